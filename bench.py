@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """Benchmark: graph-edges/sec through the WSWGAT stack fwd+bwd (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...       (driver launches N>1)
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+``--dump-outputs DIR`` also writes what the last timed step computed (the stack
+output and every gradient) as DIR/<name>.npy.  ``--full`` adds the measurements
+that take runs of their own, after the timed region: the in-step kernel times and
+rooflines, the end-to-end train step and the CPU baseline.
 
 One step = forward + backward of the HSG GAT stack W2S + n_iter x (S2W, W2S)
 (HiGraph.py:99-106, n_iter=2), all heads, FFNs included, in training mode
@@ -48,6 +54,11 @@ def parse():
                     help="GEMM operand precision: f32 (parity contract) or bf16 (config 5)")
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a HIP graph")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (stack output, gradients) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements after the timed region: in-step kernel times and "
+                         "rooflines, the end-to-end train step, the CPU baseline (the options below shape them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-docs", type=int, default=0,
                     help="docs in the CPU-baseline sample (0: the whole per-GPU batch)")
@@ -439,6 +450,29 @@ def cpu_baseline(docs, args, stack):
             "ms_per_step": dt * 1e3, "step_ms_all": [t * 1e3 for t in times]}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, tensors, seed):
+    """Write ``tensors`` (name -> tensor) as ``path``/<name>.npy, fp32 (fp64 stays fp64),
+    at most DUMP_MAX_BYTES in all: past that every array keeps the same fraction of its
+    elements, a sorted sample of its flat indices drawn from ``seed`` and the array's
+    position -- the same elements in every run with the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        arrs[name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    keep = min(1.0, DUMP_MAX_BYTES / max(total, 1))
+    for i, (name, a) in enumerate(arrs.items()):
+        if keep < 1.0:
+            n = max(1, int(a.size * keep))
+            idx = np.sort(np.random.default_rng([seed, i]).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 class HipBench:
     """The measured path: the fused WSWGAT stack of libhsg.so on this rank's ROCm
     device, captured into a HIP graph.  ``main`` drives it through these seams --
@@ -489,11 +523,13 @@ class HipBench:
         R = torch.randn(rel_w.n_dst, 64, device=dev, generator=gen)
         params = [p for p in stack.parameters() if p.requires_grad]
         from hetersumgraph_amd import rng as hsg_rng
+        last = {}
 
         def step():
             hsg_rng.advance_all()          # fresh dropout masks every step (device-side: replays too)
             s = stack(G, Xw, Xs)
             s.backward(R)                  # d/ds of sum(s * R): the upstream gradient of the stack output
+            last["stack_out"] = s.detach()     # what the caller receives (a replay rewrites it in place)
 
         def zero():
             # optimizer.zero_grad() (set_to_none): backward then writes fresh gradients
@@ -502,7 +538,18 @@ class HipBench:
             Xs.grad = None
 
         self.rel_w, self.rel_s, self.n_typed = rel_w, rel_s, rel_w.n_typed
+        self._last, self._Xs = last, Xs
         return stack, step, zero, params
+
+    def outputs(self, stack):
+        """name -> tensor of what the last step handed its caller: the stack output (the
+        final sentence states), the gradient of the encoder output Xs and of every
+        parameter (after the exchange when there is one)."""
+        out = {"stack_out": self._last["stack_out"], "grad_Xs": self._Xs.grad}
+        for name, p in stack.named_parameters():
+            if p.grad is not None:
+                out["grad_" + name] = p.grad
+        return out
 
     def capture(self, step, zero, allreduce, with_exchange):
         dev = self.dev
@@ -723,7 +770,8 @@ def main(backend_cls=HipBench):
                     else "bucketed all-reduce (concatenated copies)")
                    + (", captured in the step's HIP graph" if capture_exchange else ", eager after each step")
                    + f" ({backend}, world {world})")
-    rep = be.kernel_report(stack, step, zero, ms_per_step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, be.outputs(stack), args.seed)
 
     out = {
         "metric": "graph-edges/sec through WSWGAT fwd+bwd, CNN/DM-shaped batch; 1/2/4/8 GPU",
@@ -760,8 +808,10 @@ def main(backend_cls=HipBench):
                    "dropout": args.dropout, "parallelism": f"dp{world}", "dp_exchange": dp_exchange,
                    "hip_graph": bool(use_graph)},
     }
-    out.update(rep)
-    if world == 1 and not args.no_e2e:
+    # everything below the result's own figures takes runs of its own: --full only
+    if args.full:
+        out.update(be.kernel_report(stack, step, zero, ms_per_step))
+    if args.full and world == 1 and not args.no_e2e:
         try:
             out["e2e_train_step"] = be.e2e(G)
         except Exception as exc:  # pragma: no cover - reported in the JSON
@@ -769,7 +819,7 @@ def main(backend_cls=HipBench):
     # the CPU baseline (every GPU count beside the CPU number) on rank 0 only,
     # after the timed region and the kernel timings, on rank 0's own shard -- the same
     # per-GPU workload at every world size; the other ranks wait at a barrier
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(docs, args, stack)
         except Exception as exc:  # pragma: no cover

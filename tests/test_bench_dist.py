@@ -25,7 +25,7 @@ def test_bench_two_ranks_gloo_json_line():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "tests", "bench_cpu_worker.py"), "--gpus", "2", "--config", "cfg1",
-           "--steps", "2", "--warmup", "1", "--cpu-steps", "1", "--no-e2e"]
+           "--steps", "2", "--warmup", "1", "--full", "--cpu-steps", "1", "--no-e2e"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]

@@ -64,3 +64,26 @@ def test_dense_roofline_peak_follows_the_path():
     assert abs(r["fp32_equivalent"]["frac"] - 100.0 / bench.FP32_MFMA_PEAK_TFLOPS) < 1e-12
     b = bench.dense_roofline("hsg_gemm_*", 19200, 900.0, 5.9e9, 0.0066, "bf16")
     assert b["achieved"] == 900.0 and "fp32_equivalent" not in b
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """bench.dump_outputs: fp32 .npy files (bf16 widened, fp64 kept); past the byte
+    limit every array keeps the same fraction of its elements, the same ones for the
+    same seed."""
+    import bench
+    import torch
+    t = {"a": torch.arange(1000, dtype=torch.float32).reshape(10, 100), "b": torch.ones(40, dtype=torch.bfloat16),
+         "c": torch.arange(60, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "whole"), t, 0)
+    whole = {k: np.load(tmp_path / "whole" / f"{k}.npy") for k in t}
+    assert whole["a"].shape == (10, 100) and whole["a"].dtype == whole["b"].dtype == np.float32
+    assert whole["c"].dtype == np.float64 and np.array_equal(whole["a"], t["a"].numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1160)          # a quarter of 4000 + 160 + 480 bytes
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), t, 0)
+    s1, s2 = ({k: np.load(tmp_path / d / f"{k}.npy") for k in t} for d in ("s1", "s2"))
+    assert sum(a.nbytes for a in s1.values()) <= 1160
+    assert [s1[k].shape for k in "abc"] == [(250,), (10,), (15,)]
+    for k in t:
+        assert np.array_equal(s1[k], s2[k])
+    assert np.all(np.diff(s1["a"]) > 0) and set(s1["a"]) <= set(whole["a"].ravel())

@@ -36,8 +36,8 @@ def test_rccl_flat_exchange_captured_in_step_graph():
 
 def test_bench_dp_path_on_rccl_world1():
     env = dict(_env(), HSG_DP_REHEARSAL="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-e2e",
-                          "--no-cpu-baseline", "--kernel-reps", "5", "--kernel-steps", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                          "--no-e2e", "--no-cpu-baseline", "--kernel-reps", "5", "--kernel-steps", "2"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]

@@ -14,10 +14,10 @@
 #   traffic                 FETCH_SIZE / WRITE_SIZE passes of the roofline kernel (pmc_traffic.json)
 #   shapes                  per-shape FFN GEMM table (gemm_shapes.md)
 #   hproj                   head-projection counter passes (hproj/)
-#   benchprof               rocprofv3 --kernel-trace --stats over bench.py (trace/, bench_prof.json)
-#   bench                   the default bench line (bench.json)
-#   bench=<args>            bench.py with extra arguments, '+' for spaces (bench_<n>.json)
-#   cfgs                    bench lines of every single-GPU configuration, f32 and bf16 (cfgs/)
+#   benchprof               rocprofv3 --kernel-trace --stats over bench.py --full (trace/, bench_prof.json)
+#   bench                   the bench line with every secondary figure, bench.py --full (bench.json)
+#   bench=<args>            bench.py with extra arguments, '+' for spaces; a plain run unless --full is among them (bench_<n>.json)
+#   cfgs                    bench --full lines of every single-GPU configuration, f32 and bf16 (cfgs/)
 set -e
 TAG=$1; shift
 OUT=gpurun_out/$TAG
@@ -74,10 +74,10 @@ for step in "$@"; do
       bash tools/pmc_hproj.sh $OUT/hproj ;;
     benchprof)
       (cd /tmp && export TMPDIR=/tmp && cd $ROOT &&
-       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --no-cpu-baseline --no-e2e > $OUT/bench_prof.json 2> $OUT/bench_prof.err)
+       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --full --no-cpu-baseline --no-e2e > $OUT/bench_prof.json 2> $OUT/bench_prof.err)
       rm -f $OUT/trace/*/bench_kernel_trace.csv $OUT/trace/bench_kernel_trace.csv ;;
     bench)
-      timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err ;;
+      timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err ;;
     bench=*)
       nb=$((nb + 1))
       timeout -k 10 400 python -u bench.py $(echo ${step#bench=} | tr '+' ' ') > $OUT/bench_$nb.json 2> $OUT/bench_$nb.err ;;
@@ -85,7 +85,7 @@ for step in "$@"; do
       mkdir -p $OUT/cfgs
       for c in "cfg2 f32" "cfg2 bf16" "cfg4 f32" "cfg4 bf16" "cfg5 f32" "cfg5 bf16"; do
         set -- $c
-        timeout -k 10 240 python -u bench.py --config $1 --dtype $2 --no-cpu-baseline > $OUT/cfgs/bench_$1_$2.json 2> $OUT/cfgs/bench_$1_$2.err
+        timeout -k 10 240 python -u bench.py --full --config $1 --dtype $2 --no-cpu-baseline > $OUT/cfgs/bench_$1_$2.json 2> $OUT/cfgs/bench_$1_$2.err
       done ;;
     *) echo "unknown step $step" >&2; exit 2 ;;
   esac
