@@ -37,7 +37,7 @@ EXPORTS = ("hsg_gat_fwd", "hsg_gat_bwd_dst", "hsg_gat_bwd_blocks", "hsg_gat_bwd_
            "hsg_gat_bwd_src_g_blocks", "hsg_gemm_bf16_psw_io", "hsg_gemm_bf16_psw_elug_rho_a16", "hsg_gemm_psw_elug_rho_gw", "hsg_ln_bwd_dy16",
            "hsg_gemm_dw_slabs_io", "hsg_ln_fwd_y16", "hsg_gat_bwd_src_g_io", "hsg_rel_work", "hsg_gat_fwd_ws_floats",
            "hsg_gat_fwd_ws", "hsg_gat_bwd_src_g_ws_floats", "hsg_gat_bwd_src_g_ws", "hsg_gat_fwd_ws16",
-           "hsg_gemm_bf16_psw_elug_rho_x16", "hsg_ln_fwd_x16", "hsg_ln_bwd_x16")
+           "hsg_gemm_bf16_psw_elug_rho_x16", "hsg_ln_fwd_x16", "hsg_ln_bwd_x16", "hsg_gemm_f32_psw_plan", "hsg_gemm_f32_psw_route")
 
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
@@ -138,6 +138,8 @@ _SIGS = {
     "hsg_slab_reduce": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hsg_wsplit": [_I, _P, _P, _P, _P, _P, _P, _P],
     "hsg_gemm_f32_psw": [_I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P],
+    "hsg_gemm_f32_psw_route": [_I, _I, _I],
+    "hsg_gemm_f32_psw_plan": [_I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P],
     "hsg_gemm_f32_psw_elug": [_I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P],
     "hsg_gemm_bf16_psw": [_I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P],
     "hsg_gat_bwd_dst_g": [_RELP, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],

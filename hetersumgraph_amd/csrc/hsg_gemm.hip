@@ -998,8 +998,9 @@ struct EpiRows {
     }
 
     template <bool NS = false>    // NS: dev diagnostic, no C store (tools/gemm5_sweep.py plan 34)
+    // rmax: rows of the image that are the wave's (k_gemm13's 16-row last band)
     __device__ __forceinline__ void finish(const float *wl, int row0, int col0, int lane, const GemmArgs &p,
-                                           f32x4 &csum) {
+                                           f32x4 &csum, int rmax = 32) {
         __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): the wave's own LDS writes
         __builtin_amdgcn_wave_barrier();
         const int q = lane % QS, rs = lane / QS;
@@ -1018,7 +1019,7 @@ struct EpiRows {
 #pragma unroll
         for (int t = 0; t < STEPS; ++t) {
             const int r = t * RPS + rs, m = row0 + r;
-            const bool rok = r < 32 && m < p.M;
+            const bool rok = r < rmax && m < p.M;
             float c[3] = {0.f, 0.f, 0.f};
             if (qok && rok) {
                 f32x4 v = *reinterpret_cast<const f32x4 *>(&wl[r * LDW + 4 * q]);
@@ -1293,8 +1294,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm5(GemmArgs p, const __bf16 *__re
 // 16x16x32 lane map under gfx950's ds_read_b128 lane groups; round 4's k_gemm5
 // swizzles cost 2-way conflicts on every read).
 // The epilogue goes through LDS (epi_rows: float4 aux loads and C stores).  Measured
-// (tools/gemm5_sweep.py, 5 interleaved rounds): BN = 64 is the fastest tile on all
-// four cfg2 S2W FFN shapes; the wide tiles (80 | 128) were not faster.
+// (tools/gemm5_sweep.py, 5 interleaved rounds): of THIS kernel's tiles BN = 64 was the
+// fastest on all four cfg2 S2W FFN shapes (80 | 128 were not faster); since then the
+// N <= 320 shapes run 112-wide where that saves a round (wide112_pays) and the N > 320
+// shapes run on k_gemm13's 64-column wave tiles where its grid is one round (gemm13_pays).
 // ---------------------------------------------------------------------------------
 
 // PM: 0 = fp32-accurate (RNE 3-limb split, six products), 1 = the same with the
@@ -1529,6 +1532,198 @@ int launch7(GemmArgs p, const __bf16 *planes, int Np, int Kp, hipStream_t st) {
     hipLaunchKernelGGL((k_gemm7<BN, S, PM, OCC, SA, IO>), dim3((unsigned)g), dim3(256), 0, st, p, planes, Np, Kp);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
+}
+
+// ---------------------------------------------------------------------------------
+// k_gemm13: k_gemm7's contract and products (fp32 A split by split_rne8, the weight's
+// limb planes, six products per subtile pair in k_gemm7's order, 32-deep K steps in
+// order, no split-K: C and colsum_part are bitwise k_gemm7<64>'s) on 64-column WAVE
+// tiles: block = 32 TM rows x 128 columns, 2 x 2 waves, each wave TM x 4 subtiles of
+// 16 x 16.  Per K step a wave reads the A fragments of its 16 TM rows once (2 TM
+// ds_read_b128) and the B fragments of its 64 columns once (12): 0.15-0.17 reads per
+// MFMA against k_gemm7's 0.33, and 20 TM + 24 KB staged per 24 TM MFMAs x 4 waves.
+// ONE stage: a K step reads every fragment into registers (raw fp32 A: the split runs
+// per row subtile in front of its 24 MFMAs), a second barrier frees the stage, and the
+// DMA pieces of the next tile are issued one A and one B piece per row subtile, between
+// the MFMA runs (issued in one lump in front of them they cost 4-6 us per launch).  One
+// stage of 160 | 192 x 128 is 44 | 48 KB, so two blocks per CU keep a whole tile each in
+// flight (k_gemm7: 28 KB per block); two 32-deep stages of these tiles exceed 80 KB.
+// Rows: TM = 5 (BM = 160) without colsum_part, TM = 6 (BM = 192) with it -- its slabs
+// are 64 rows in global row order and a slab's sum runs over its two 32-row bands in
+// order (epi_rows_colpart), so a 160-row block would split a slab between two blocks.
+// N = 512 at cfg2 (M = 19,200): 480 | 400 blocks, ONE round of the 512 resident.
+// The epilogue is k_gemm7<64>'s, a 32-row band (TM = 5: the last one 16 rows) at a time
+// through the wave's own 32 x 68 row image (EpiRows<64>), which reuses the stage; a
+// band's global operands are requested while the band before it is stored.
+// ---------------------------------------------------------------------------------
+template <int TM>
+__global__ __launch_bounds__(256, 2) void k_gemm13(GemmArgs p, const __bf16 *__restrict__ planes, int Np, int Kp) {
+    constexpr int BM = 32 * TM, BN = 128, WM = 16 * TM, NB = (TM + 1) / 2;
+    constexpr int A_FL = BM * 32;                          // floats of the A tile
+    constexpr int B_BF = BN * 32;                          // bf16 per limb-plane tile
+    constexpr int STAGE_FL = A_FL + 3 * B_BF / 2;
+    constexpr int EPI_FL = 4 * 32 * 68;                    // four waves' row images
+    constexpr int RED_FL = TM % 2 == 0 ? (BM / 32) * 4 * BN : 0;   // per-band, per-row-step column sums
+    __shared__ __attribute__((aligned(16))) float lds[STAGE_FL > EPI_FL + RED_FL ? STAGE_FL : EPI_FL + RED_FL];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wr = wid >> 1, wc = wid & 1;
+    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
+    const int total = tiles_n * tiles_m;
+    const int lt = p.xcd ? xcd_tile(blockIdx.x, total) : (int)blockIdx.x;
+    const int tx = lt % tiles_n, ty = lt / tiles_n;
+    const int m0 = ty * BM, n0 = tx * BN;
+    const int nt = Kp / 32;
+    __builtin_assume(p.epi != HSG_EPI_ADD_ELUG);           // (host-checked) no ELU-gate operands to hold
+
+    f32x4v7 acc[TM][4];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4v7{0.f, 0.f, 0.f, 0.f};
+
+    // piece pc of the wave's DMA share of K tile it: one 1-KB piece of A (8 rows; TM per
+    // wave) and one of the weight planes (16 rows of a limb; 3 limbs x 8 pieces, 6 per wave)
+    auto issue_a = [&](int it, int pc) {
+        const int piece = pc * 4 + wid;
+        const int r = piece * 8 + (lane >> 3);
+        const int k = it * 32 + 4 * ((lane & 7) ^ swz16(r));
+        const float *src = k < p.K ? p.A + (size_t)min(m0 + r, p.M - 1) * p.lda + k : g_zero16;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                                         (__attribute__((address_space(3))) void *)(lds + piece * 256), 16, 0, 0);
+    };
+    auto issue_b = [&](int it, int pc) {
+        __bf16 *sb = reinterpret_cast<__bf16 *>(lds + A_FL);
+        const int piece = pc * 4 + wid;
+        const int limb = piece / 8, prow = (piece % 8) * 16;
+        const int r = prow + (lane >> 2);
+        const int c = (lane & 3) ^ bswz16(r);
+        const __bf16 *src = planes + ((size_t)(limb * Np + n0 + r) * Kp + it * 32 + 8 * c);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                                         (__attribute__((address_space(3))) void *)(sb + limb * B_BF + prow * 32),
+                                         16, 0, 0);
+    };
+    if (nt > 0) {
+#pragma unroll
+        for (int pc = 0; pc < TM; ++pc) issue_a(0, pc);
+#pragma unroll
+        for (int pc = 0; pc < 6; ++pc) issue_b(0, pc);
+    }
+    const int li = lane & 15, kb = lane >> 4;
+    const __bf16 *sb = reinterpret_cast<const __bf16 *>(lds + A_FL);
+    for (int it = 0; it < nt; ++it) {
+        wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();                       // tile it has landed
+        asm volatile("" ::: "memory");
+        f32x4 ax[TM], ay[TM];
+        bf16x8 b[4][3];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int r = wr * WM + 16 * i + li, sw = swz16(r);
+            ax[i] = *reinterpret_cast<const f32x4 *>(&lds[r * 32 + 4 * ((2 * kb) ^ sw)]);
+            ay[i] = *reinterpret_cast<const f32x4 *>(&lds[r * 32 + 4 * ((2 * kb + 1) ^ sw)]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = wc * 64 + 16 * j + li;
+            const int off = r * 32 + 8 * (kb ^ bswz16(r));
+#pragma unroll
+            for (int l = 0; l < 3; ++l) b[j][l] = *reinterpret_cast<const bf16x8 *>(&sb[l * B_BF + off]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                       // every wave holds its fragments
+        asm volatile("" ::: "memory");
+        const bool more = it + 1 < nt;                      // the next tile lands under the MFMAs below
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            bf16x8 a0, a1, a2;
+            if (more) {
+                issue_a(it + 1, i);
+                issue_b(it + 1, i);
+                if (i == TM - 1)
+                    for (int pc = TM; pc < 6; ++pc) issue_b(it + 1, pc);
+            }
+            split_rne8(ax[i], ay[i], a0, a1, a2);
+            // per accumulator k_gemm7's order (small products first); the four column
+            // subtiles interleaved, so neighbouring MFMAs are independent
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b[j][0], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b[j][1], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[j][2], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b[j][0], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[j][1], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[j][0], acc[i][j], 0, 0, 0);
+        }
+    }
+
+    // k_gemm7<64>'s epilogue per 32-row band of the wave's 64 columns
+    __syncthreads();
+    float *wl = lds + wid * 32 * 68;
+    const int c = lane & 15, rq = 4 * (lane >> 4);
+    const int col0 = n0 + wc * 64;
+    EpiRows<64> eps[NB];
+    eps[0].load(p, m0 + wr * WM, col0, lane);
+#pragma unroll
+    for (int bd = 0; bd < NB; ++bd) {
+        const int row0 = m0 + wr * WM + 32 * bd;
+        const int rows = WM - 32 * bd < 32 ? WM - 32 * bd : 32;             // 16 in an odd TM's last band
+        if (bd + 1 < NB) eps[bd + 1].load(p, row0 + 32, col0, lane);       // the next band's operands
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (2 * bd + i < TM) wl[(16 * i + rq + e) * 68 + 16 * j + c] = acc[2 * bd + i < TM ? 2 * bd + i : 0][j][e];
+        f32x4 cs;
+        eps[bd].finish(wl, row0, col0, lane, p, cs, rows);
+        if constexpr (TM % 2 == 0) {
+            // band (wr NB + bd) of the block, row step lane / 16: epi_rows_colpart's layout
+            if (p.colpart)
+                *reinterpret_cast<f32x4 *>(&lds[EPI_FL + ((wr * NB + bd) * 4 + (lane >> 4)) * BN + wc * 64 +
+                                                4 * (lane & 15)]) = cs;
+        }
+        __builtin_amdgcn_wave_barrier();                    // the image is read before the next band's writes
+    }
+    if constexpr (TM % 2 == 0) {
+        if (p.colpart) {                                    // 64-row slabs in epi_rows_colpart's order
+            const float *red = lds + EPI_FL;
+            __syncthreads();
+            const int rows64 = (p.M + 63) / 64;
+            for (int cc = threadIdx.x; cc < (BM / 64) * BN; cc += 256) {
+                const int s = cc / BN, col = cc % BN, n = n0 + col, slab = ty * (BM / 64) + s;
+                float v = 0.f;
+                for (int w = 2 * s; w < 2 * s + 2; ++w)
+                    for (int r = 0; r < 4; ++r) v += red[(w * 4 + r) * BN + col];
+                if (n < p.N && slab < rows64) p.colpart[(size_t)slab * p.N + n] = v;
+            }
+        }
+    }
+}
+
+template <int TM>
+int launch13(GemmArgs p, const __bf16 *planes, int Np, int Kp, hipStream_t st) {
+    constexpr int BM = 32 * TM;
+    p.splits = 1;
+    p.k_tiles_per_split = Kp / 32;
+    if ((p.N + 127) / 128 * 128 > Np) return HSG_EINVAL;    // B tile rows must exist in the planes
+    if (!epi_rows_ok(p)) return HSG_EINVAL;                 // the float4 epilogue needs whole aligned quads
+    if (p.colpart && BM % 64) return HSG_EINVAL;            // 64-row column partials
+    const long g = (long)((p.N + 127) / 128) * ((p.M + BM - 1) / BM);
+    hipLaunchKernelGGL((k_gemm13<TM>), dim3((unsigned)g), dim3(256), 0, st, p, planes, Np, Kp);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+// the block rows k_gemm13 runs a call at
+int gemm13_bm(const GemmArgs &p) { return p.colpart ? 192 : 160; }
+int launch13(GemmArgs p, const __bf16 *planes, int Np, int Kp, hipStream_t st) {
+    return p.colpart ? launch13<6>(p, planes, Np, Kp, st) : launch13<5>(p, planes, Np, Kp, st);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2106,6 +2301,22 @@ bool wide112_pays(int M, int N) {
     const long slots = 2L * cus, mt = (M + 127) / 128;
     const long r112 = (mt * ((N + 111) / 112) + slots - 1) / slots, r64 = (mt * ((N + 63) / 64) + slots - 1) / slots;
     return r112 * 112 < r64 * 64;
+}
+
+// k_gemm13's bm x 128 tiles (bm = 160, or 192 with colsum_part) against k_gemm7's
+// 128 x 64 for N > 320: slot-rounds x tile work, as above, with k_gemm13's work per
+// output at 9/10 of k_gemm7's -- measured at equal work per slot (cfg2's N = 512 shapes:
+// one round of 192 x 128 in 42.6 / 41.8 us against three of 128 x 64 in 47.6 / 47.5).
+// cfg2 (M = 19,200): 480 | 400 tiles in ONE round against 1,200 in three; a shape whose
+// k_gemm7 grid is two rounds or fewer keeps k_gemm7, and so does one that would need a
+// second round of the big tiles (cfg5, M = 28,800: 720 | 600 tiles).
+bool gemm13_pays(int M, int N, int bm) {
+    if (N <= 320) return false;
+    const int cus = device_cus() > 0 ? device_cus() : 256;
+    const long slots = 2L * cus;
+    const long r13 = (((M + bm - 1) / bm) * (long)((N + 127) / 128) + slots - 1) / slots;
+    const long r7 = (((M + 127) / 128) * (long)((N + 63) / 64) + slots - 1) / slots;
+    return r13 * bm * 128 * 9 < r7 * 128 * 64 * 10;
 }
 
 template <int BM, int BN, int WGM, int WGN, int PM, int S = 2, int OCC = 1>
@@ -2794,6 +3005,22 @@ int hsg_wsplit(int njobs, const float *const *W, const int *N, const int *K, con
 int hsg_gemm_f32_psw(int M, int N, int K, const float *A, int lda, const void *planes, float *C, int ldc,
                      const float *bias, const float *aux, int ldaux, int epi, int relu, float *colsum_part,
                      void *stream) {
+    return hsg_gemm_f32_psw_plan(M, N, K, A, lda, planes, C, ldc, bias, aux, ldaux, epi, relu, colsum_part, 0, stream);
+}
+
+// the router's kernel for aligned operands without colsum_part: 13 = k_gemm13, 7 =
+// k_gemm7 (either width)
+int hsg_gemm_f32_psw_route(int M, int N, int K) {
+    (void)K;
+    return gemm13_pays(M, N, 160) ? 13 : 7;
+}
+
+// sel: 0 = the router below, 7 = k_gemm7<64>, 13 = k_gemm13 (tests and A/B runs; no
+// environment variable is read for it)
+int hsg_gemm_f32_psw_plan(int M, int N, int K, const float *A, int lda, const void *planes, float *C, int ldc,
+                          const float *bias, const float *aux, int ldaux, int epi, int relu, float *colsum_part,
+                          int sel, void *stream) {
+    if (sel != 0 && sel != 7 && sel != 13) return HSG_EINVAL;
     if (M < 0 || N < 0 || K < 0 || !C || !planes || !A) return HSG_EINVAL;
     if (epi != HSG_EPI_STORE && epi != HSG_EPI_RELU_BWD && epi != HSG_EPI_ADD) return HSG_EINVAL;
     if (epi != HSG_EPI_STORE && !aux) return HSG_EINVAL;
@@ -2811,6 +3038,8 @@ int hsg_gemm_f32_psw(int M, int N, int K, const float *A, int lda, const void *p
     // golden's gradient gate-flip row left its tolerance with it.
     const __bf16 *pl = reinterpret_cast<const __bf16 *>(planes);
     hipStream_t st = (hipStream_t)stream;
+    if (sel == 7) return epi_rows_ok(p) ? launch7<64, 2>(p, pl, Np, Kp, st) : HSG_EINVAL;
+    if (sel == 13) return launch13(p, pl, Np, Kp, st);
 #ifdef HSG_DEV
     int plan = 27;
     if (const char *f = HSG_DEV_ENV("HSG_GEMM5")) plan = atoi(f);
@@ -2863,6 +3092,7 @@ int hsg_gemm_f32_psw(int M, int N, int K, const float *A, int lda, const void *p
     // and each wave's A split feeds 7 instead of 4 column subtiles: 44.1 -> 39.1 us back
     // to back (tools/gemm5_sweep.py, plan 42 against 27; same products, bitwise)
     // (where the planes' padded rows cover the 112-wide tiles; else 64)
+    if (epi_rows_ok(p) && gemm13_pays(M, N, gemm13_bm(p))) return launch13(p, pl, Np, Kp, st);
     if (epi_rows_ok(p))
         return N <= 320 && (N + 111) / 112 * 112 <= Np && wide112_pays(M, N) ? launch7<112, 2>(p, pl, Np, Kp, st)
                                                                              : launch7<64, 2>(p, pl, Np, Kp, st);

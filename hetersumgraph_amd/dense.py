@@ -151,14 +151,15 @@ def _io(A, out, aux):
             | (_lib.HSG_IO_AUX_BF16 if aux is not None and aux.dtype == bf else 0))
 
 
-def gemm_psw(A, Bs, out=None, bias=None, relu=False, relu_mask=None, add=None, colsum_part=None):
+def gemm_psw(A, Bs, out=None, bias=None, relu=False, relu_mask=None, add=None, colsum_part=None, plan=0):
     """C = A @ B^T [+ bias] [relu] | * (relu_mask > 0) | + add, with B a SplitWeight
     (hsg_gemm_f32_psw: fp32-accurate as gemm(..., dtype='f32'); a weight split in the
     'bf16' mode runs hsg_gemm_bf16_psw: its plane 0 = RNE(W), one bf16 product, as
     gemm(..., dtype='bf16')).  In the 'bf16' mode A, ``out`` and ``relu_mask`` may be
     bf16 tensors (the FFN's bf16 activations, hsg_gemm_bf16_psw_io): the same products,
     since that mode rounds A to bf16 anyway; a bf16 A carries zeros in its columns K ..
-    ceil8(K) - 1 (row pitch a multiple of 8)."""
+    ceil8(K) - 1 (row pitch a multiple of 8).  ``plan`` (fp32 mode only) names the kernel
+    (hsg_gemm_f32_psw_plan: 0 = the library's choice, 7, 13; tests and A/B timing)."""
     lib = load()
     if not A.is_cuda or A.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError("hsg gemm: fp32 ROCm tensors only (no CPU fallback)")
@@ -174,6 +175,8 @@ def gemm_psw(A, Bs, out=None, bias=None, relu=False, relu_mask=None, add=None, c
     elif add is not None:
         epi, aux = HSG_EPI_ADD, add
     io = _io(A, out, aux)
+    if plan and (io or Bs.mode == "bf16"):
+        raise ValueError("gemm_psw: plan selects among the fp32 mode's kernels only")
     if io:
         if Bs.mode != "bf16":
             raise RuntimeError("gemm_psw: bf16 activations belong to the 'bf16' GEMM mode")
@@ -192,9 +195,9 @@ def gemm_psw(A, Bs, out=None, bias=None, relu=False, relu_mask=None, add=None, c
                         splits=1 if colsum_part is not None else 0, colsum_part=colsum_part, dtype="bf16")
         check(rc, "hsg_gemm_bf16_psw")
         return out
-    check(lib.hsg_gemm_f32_psw(M, N, K, ptr(A), _ld(A), ptr(Bs.planes), ptr(out), _ld(out), ptr(bias), ptr(aux),
-                               _ld(aux) if aux is not None else 0, epi, int(relu), ptr(colsum_part),
-                               stream_of(A)), "hsg_gemm_f32_psw")
+    check(lib.hsg_gemm_f32_psw_plan(M, N, K, ptr(A), _ld(A), ptr(Bs.planes), ptr(out), _ld(out), ptr(bias), ptr(aux),
+                                    _ld(aux) if aux is not None else 0, epi, int(relu), ptr(colsum_part),
+                                    int(plan), stream_of(A)), "hsg_gemm_f32_psw_plan")
     return out
 
 

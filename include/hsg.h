@@ -313,6 +313,20 @@ int hsg_wsplit(int njobs, const float *const *W, const int *N, const int *K, con
 int hsg_gemm_f32_psw(int M, int N, int K, const float *A, int lda, const void *planes,
                      float *C, int ldc, const float *bias, const float *aux, int ldaux,
                      int epi, int relu, float *colsum_part, void *stream);
+/* hsg_gemm_f32_psw with the kernel named (tests and A/B timing; reads no environment
+ * variable).  plan: 0 = the library's own choice (hsg_gemm_f32_psw), 7 = 128 x 64 blocks
+ * of 32 x 64 wave tiles, 13 = 160 x 128 blocks of 80 x 64 wave tiles (192 x 128 of
+ * 96 x 64 with colsum_part, whose slabs are 64 rows): the choice for N > 320 where that
+ * grid is the cheaper one.  Both need N % 4 == 0 and 16-byte aligned C / bias / aux rows
+ * (HSG_EINVAL otherwise, and for any other plan value).  C and colsum_part are bitwise
+ * the same under every plan. */
+int hsg_gemm_f32_psw_plan(int M, int N, int K, const float *A, int lda, const void *planes,
+                          float *C, int ldc, const float *bias, const float *aux, int ldaux,
+                          int epi, int relu, float *colsum_part, int plan, void *stream);
+/* The plan hsg_gemm_f32_psw takes for this shape with aligned operands and no
+ * colsum_part: 7 or 13 (the rule counts the device's compute units; no kernel is
+ * launched). */
+int hsg_gemm_f32_psw_route(int M, int N, int K);
 /* The FFN backward's last GEMM with the edge layer's ELU gate fused into its epilogue
  * (GAT.py:56-57 backward; replaces the dOut -> G step of hsg_gat_bwd_dst):
  *   C = aux + A B^T          (dx = ds + dH W1: the FFN input's gradient, = the origin's)

@@ -54,6 +54,20 @@ def gemm7_b(sw):
             for j in range(4)]
 
 
+def gemm13_a(tm=6):
+    """k_gemm13 A image (rows of 128 B, swz16): wave row wr owns rows 16 tm wr .. + 16 tm."""
+    return [extra_cycles(lambda l: (wr * 16 * tm + 16 * i + (l & 15)) * 32
+                         + 4 * ((2 * (l >> 4) + half) ^ swz16(wr * 16 * tm + 16 * i + (l & 15))))
+            for wr in range(2) for i in range(tm) for half in range(2)]
+
+
+def gemm13_b():
+    """k_gemm13 weight limb plane of 128 rows (64 B, bswz16): wave column wc reads rows 64 wc + 16 j."""
+    return [extra_cycles(lambda l: (64 * wc + 16 * j + (l & 15)) * 16
+                         + 4 * ((l >> 4) ^ bswz16(64 * wc + 16 * j + (l & 15))))
+            for wc in range(2) for j in range(4)]
+
+
 def gemm5_a():
     """k_gemm5 A image, 32x32x16 map (lane = 32 h + row)."""
     return [extra_cycles(lambda l: (wid * 32 + (l & 31)) * 32 + 4 * ((4 * s16 + 2 * (l >> 5) + half) ^ swz(l & 31)))
@@ -105,6 +119,8 @@ def main():
         ("k_gemm7 A, swz16", gemm7_a(swz16)),
         ("k_gemm7 B, round-4 (r>>2)&3", gemm7_b(lambda r: (r >> 2) & 3)),
         ("k_gemm7 B, bswz16", gemm7_b(bswz16)),
+        ("k_gemm13 A (192 rows), swz16", gemm13_a()),
+        ("k_gemm13 B (128 rows), bswz16", gemm13_b()),
         ("k_gemm5 A (32x32x16)", gemm5_a()),
         ("k_gemm5 B (32x32x16)", gemm5_b()),
     ]
