@@ -19,7 +19,9 @@ import torch
 import torch.nn as nn
 import torch.nn.utils.rnn as rnn
 
+from . import _lib
 from .graph import TableColumn
+from .lstm import native_lstm_ok, sent_lstm
 from .module.Encoder import sentEncoder
 from .module.GAT import WSWGAT
 from .module.GATLayer import CHECK_NAN, TFIDF_TAG
@@ -156,7 +158,13 @@ class HSumGraph(nn.Module):
         """HiGraph.py:135-142 on the documents' sentence rows laid end to end.  The
         padding to [docs, max_len] and the gather of the valid rows back are one index
         scatter and one index gather (positions cached) instead of a copy per document
-        each way; the same values move, so the result is the reference's bit for bit."""
+        each way; the same values move, so the result is the reference's bit for bit.
+
+        Opt-in (``path_options(HSG_SENT_LSTM="1")``): the native recurrence kernels of
+        :mod:`hetersumgraph_amd.lstm` where they cover the call."""
+        if (ngram.is_cuda and _lib.path_option("HSG_SENT_LSTM", "0") == "1"
+                and native_lstm_ok(ngram, self.lstm)):
+            return self.lstm_proj(sent_lstm(ngram, glen, self.lstm))
         n_doc, max_len = len(glen), max(glen)
         key = ("lstm_index", tuple(glen))
         idx = getattr(self, "_lstm_idx", None)

@@ -37,7 +37,8 @@ EXPORTS = ("hsg_gat_fwd", "hsg_gat_bwd_dst", "hsg_gat_bwd_blocks", "hsg_gat_bwd_
            "hsg_gat_bwd_src_g_blocks", "hsg_gemm_bf16_psw_io", "hsg_gemm_bf16_psw_elug_rho_a16", "hsg_gemm_psw_elug_rho_gw", "hsg_ln_bwd_dy16",
            "hsg_gemm_dw_slabs_io", "hsg_ln_fwd_y16", "hsg_gat_bwd_src_g_io", "hsg_rel_work", "hsg_gat_fwd_ws_floats",
            "hsg_gat_fwd_ws", "hsg_gat_bwd_src_g_ws_floats", "hsg_gat_bwd_src_g_ws", "hsg_gat_fwd_ws16",
-           "hsg_gemm_bf16_psw_elug_rho_x16", "hsg_ln_fwd_x16", "hsg_ln_bwd_x16", "hsg_gemm_f32_psw_plan", "hsg_gemm_f32_psw_route")
+           "hsg_gemm_bf16_psw_elug_rho_x16", "hsg_ln_fwd_x16", "hsg_ln_bwd_x16", "hsg_gemm_f32_psw_plan", "hsg_gemm_f32_psw_route",
+           "hsg_lstm_supported", "hsg_lstm_fwd", "hsg_lstm_bwd")
 
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
@@ -161,8 +162,11 @@ _SIGS = {
     "hsg_gemm_bf16_psw_elug_rho_x16": [_I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _P],
     "hsg_ln_fwd_x16": [_I, _I, _P, _P, _I, _P, _P, _F, _F, _P, ctypes.c_uint32, _P, _P, _P, _P],
     "hsg_ln_bwd_x16": [_I, _I, _P, _P, _P, _I, _P, _P, _P, _F, _P, ctypes.c_uint32, _P, _I, _P, _P, _P],
+    "hsg_lstm_supported": [_I, _I],
+    "hsg_lstm_fwd": [_I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _F, _P, ctypes.c_uint32, _P, _I, _P],
+    "hsg_lstm_bwd": [_I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _F, _P, ctypes.c_uint32, _P, _P],
     "hsg_gat_bwd_src_g_ws_floats": [_RELP, _I, _I],
-    "hsg_gat_bwd_src_g_ws": [_RELP, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "hsg_gat_bwd_src_g_ws":[_RELP, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 _RESTYPE = {"hsg_version": ctypes.c_char_p, "hsg_wsplit_dims": None, "hsg_gemm_workspace_floats": ctypes.c_size_t,
             "hsg_attn_params_bwd_workspace_floats": ctypes.c_size_t,

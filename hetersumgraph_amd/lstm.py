@@ -1,0 +1,227 @@
+"""The sentence encoder's LSTM on the native recurrence kernels (C ABI: hsg_lstm_fwd /
+hsg_lstm_bwd, csrc/hsg_lstm.hip).
+
+Reference: HiGraph.py:117-123 builds ``nn.LSTM(300, 128, num_layers=2,
+bidirectional=True, dropout=0.1)`` and HiGraph.py:135-142 runs it over each document's
+padded, packed sentence sequence.  :func:`sent_lstm` computes the same layer stack on
+the documents' sentence rows laid end to end (no padding, no packing), as ONE autograd
+node: per layer one input-projection GEMM (both directions' ``W_ih`` stacked), one
+recurrence launch with a block per (document, direction), and in the backward one
+reverse recurrence launch plus the weight-gradient GEMMs.  All GEMMs are
+:func:`hetersumgraph_amd.dense.gemm` with ``dtype="f32"``, whatever the process-wide
+GEMM mode.  Parameters are read from the ``nn.LSTM`` module itself, so state_dict keys
+and checkpoints do not change.
+
+In train mode the dropout between layers draws its keep-mask from the project's
+counter hash (:mod:`hetersumgraph_amd.rng`, the FFN dropout generator over the
+row-major element index) instead of the vendor RNN's dropout state: one
+``(seed snapshot, offset)`` per dropped layer output, shared by forward and backward.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import rng
+from ._lib import check, load, ptr, stream_of
+from .dense import gemm
+from .reduce import SlabBatch
+
+_LAYOUTS = {}
+_MAX_LAYOUTS = 64
+
+
+class DocLayout:
+    """Row layout of one batch: ``doc_off`` (device int32 [n_docs + 1]) and ``prev``
+    (int64 [n_rows, 2]: the row holding h_{t-1} of direction 0 / 1, ``n_rows`` -- a zero
+    row -- at a sequence start)."""
+    __slots__ = ("glen", "n_docs", "n_rows", "doc_off", "prev")
+
+    def __init__(self, glen, device):
+        self.glen = glen
+        self.n_docs, self.n_rows = len(glen), int(sum(glen))
+        off = torch.zeros(self.n_docs + 1, dtype=torch.int64)
+        if self.n_docs:
+            off[1:] = torch.cumsum(torch.tensor(glen, dtype=torch.int64), 0)
+        n = self.n_rows
+        r = torch.arange(n, dtype=torch.int64)
+        doc = torch.repeat_interleave(torch.arange(self.n_docs), torch.tensor(glen, dtype=torch.int64))
+        p0 = torch.where(r > off[:-1][doc], r - 1, torch.full_like(r, n))
+        p1 = torch.where(r < off[1:][doc] - 1, r + 1, torch.full_like(r, n))
+        self.doc_off = off.to(torch.int32).to(device)
+        self.prev = torch.stack([p0, p1], 1).to(device)
+
+
+def doc_layout(glen, device) -> DocLayout:
+    """The cached :class:`DocLayout` of a batch, keyed by the ``glen`` tuple (and the
+    device): built on the host once, so a step needs no host readback."""
+    device = torch.device(device)
+    key = (tuple(int(g) for g in glen), str(device))
+    lay = _LAYOUTS.get(key)
+    if lay is None:
+        if any(g < 0 for g in key[0]):
+            raise ValueError("sent_lstm: negative document length")
+        if len(_LAYOUTS) >= _MAX_LAYOUTS:
+            _LAYOUTS.clear()
+        lay = _LAYOUTS[key] = DocLayout(key[0], device)
+    return lay
+
+
+def doc_offsets(glen, device):
+    """Device int32 [n_docs + 1] row offsets of the documents (cached per ``glen``)."""
+    return doc_layout(glen, device).doc_off
+
+
+def native_lstm_ok(rows, lstm) -> bool:
+    """Whether :func:`sent_lstm` covers this call: fp32 rows on a ROCm device, a shape
+    the kernels take (hsg_lstm_supported), batch_first, no projection."""
+    if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2):
+        return False
+    if not (isinstance(lstm, torch.nn.LSTM) and lstm.batch_first and lstm.proj_size == 0 and lstm.bias):
+        return False
+    if rows.shape[1] != lstm.input_size or lstm.input_size % 4:
+        return False
+    return bool(load().hsg_lstm_supported(int(lstm.hidden_size), 2 if lstm.bidirectional else 1))
+
+
+def _names(layer, ndir):
+    for d in range(ndir):
+        sfx = f"_l{layer}" + ("_reverse" if d else "")
+        yield tuple(n + sfx for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+
+
+def lstm_params(lstm):
+    """The module's parameters in (layer, direction, w_ih, w_hh, b_ih, b_hh) order."""
+    ndir = 2 if lstm.bidirectional else 1
+    return [getattr(lstm, n) for layer in range(lstm.num_layers) for names in _names(layer, ndir) for n in names]
+
+
+def _layer_fwd(x, lay, ndir, hid, wih, whh, bias, p, draw):
+    """One layer: (hbuf [n + 1, ndir*hid] with a zero last row, gates, c, y or None)."""
+    lib = load()
+    n = lay.n_rows
+    pre = gemm(x, wih, b_t=True, bias=bias, dtype="f32")
+    hbuf = x.new_empty(n + 1, ndir * hid)
+    hbuf[n].zero_()
+    gates = x.new_empty(n, ndir * 4 * hid)
+    c = x.new_empty(n, ndir * hid)
+    y = x.new_empty(n, ndir * hid) if p > 0 else None
+    seed, off = draw if p > 0 else (None, 0)
+    check(lib.hsg_lstm_fwd(lay.n_docs, n, hid, ndir, ptr(lay.doc_off), ptr(pre), pre.stride(0), ptr(whh), ptr(hbuf),
+                           hbuf.stride(0), ptr(gates), ptr(c), float(p), ptr(seed), off, ptr(y),
+                           y.stride(0) if y is not None else 0, stream_of(x)), "hsg_lstm_fwd")
+    return hbuf, gates, c, y
+
+
+def _stacked(params, layer, ndir):
+    """(W_ih [ndir*4*hid, in], W_hh [ndir, 4*hid, hid], b_ih + b_hh [ndir*4*hid]) of a layer."""
+    ps = [params[(layer * ndir + d) * 4:(layer * ndir + d) * 4 + 4] for d in range(ndir)]
+    wih = torch.cat([q[0] for q in ps], 0) if ndir > 1 else ps[0][0].contiguous()
+    whh = torch.stack([q[1] for q in ps], 0).contiguous()
+    bias = torch.cat([q[2] + q[3] for q in ps], 0)
+    return wih, whh, bias
+
+
+def _forward(rows, lay, spec, params, draws):
+    """All layers.  Returns per layer (x, wih, whh, hbuf, gates, c, y)."""
+    n_layers, ndir, hid, p = spec
+    x, out = rows, []
+    for layer in range(n_layers):
+        wih, whh, bias = _stacked(params, layer, ndir)
+        pl = p if layer < n_layers - 1 else 0.0
+        hbuf, gates, c, y = _layer_fwd(x, lay, ndir, hid, wih, whh, bias, pl, draws[layer])
+        out.append((x, wih, whh, hbuf, gates, c, y))
+        x = y if y is not None else hbuf[:lay.n_rows]
+    return out
+
+
+class _SentLSTM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, lay, spec, draws, *params):
+        n_layers = spec[0]
+        with torch.no_grad():
+            layers = _forward(rows, lay, spec, [q.detach() for q in params], draws)
+        saved = []
+        for x, wih, whh, hbuf, gates, c, y in layers:
+            saved += [x, wih, whh, hbuf, gates, c]
+        saved += [d[0] for d in draws if d is not None]
+        ctx.save_for_backward(*saved)
+        ctx.lay, ctx.spec = lay, spec
+        ctx.offsets = [None if d is None else d[1] for d in draws]
+        return layers[n_layers - 1][3][:lay.n_rows]
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = load()
+        lay, (n_layers, ndir, hid, p) = ctx.lay, ctx.spec
+        saved = ctx.saved_tensors
+        seeds = list(saved[6 * n_layers:])
+        seed_of = [None] * n_layers
+        for layer in range(n_layers):
+            if ctx.offsets[layer] is not None:
+                seed_of[layer] = seeds.pop(0)
+        n, G = lay.n_rows, 4 * hid
+        grads = [None] * (4 * n_layers * ndir)
+        red = SlabBatch()
+        dcur = dout.contiguous()
+        for layer in range(n_layers - 1, -1, -1):
+            x, wih, whh, hbuf, gates, c = saved[6 * layer:6 * layer + 6]
+            pl = p if seed_of[layer] is not None else 0.0
+            dg = x.new_empty(n, ndir * G)
+            check(lib.hsg_lstm_bwd(lay.n_docs, n, hid, ndir, ptr(lay.doc_off), ptr(dcur), dcur.stride(0), ptr(gates),
+                                   ptr(c), ptr(whh), float(pl), ptr(seed_of[layer]), ctx.offsets[layer] or 0, ptr(dg),
+                                   stream_of(x)), "hsg_lstm_bwd")
+            dwih = gemm(dg, x, a_t=True, dtype="f32")
+            hprev = hbuf.view(n + 1, ndir, hid).gather(
+                0, lay.prev[:, :ndir].unsqueeze(2).expand(n, ndir, hid)).view(n, ndir * hid)
+            db = x.new_empty(ndir * G)
+            red.add(("db", layer), db, ndir * G, ndir * G, 0, 1.0, False, dg, n)
+            for d in range(ndir):
+                dwhh = gemm(dg[:, d * G:(d + 1) * G], hprev[:, d * hid:(d + 1) * hid], a_t=True, dtype="f32")
+                b = (layer * ndir + d) * 4
+                grads[b], grads[b + 1] = dwih[d * G:(d + 1) * G], dwhh
+                grads[b + 2] = grads[b + 3] = db[d * G:(d + 1) * G]
+            if layer > 0 or ctx.needs_input_grad[0]:
+                dcur = gemm(dg, wih, dtype="f32")
+            else:
+                dcur = None
+        red.flush()
+        return (dcur, None, None, None) + tuple(grads)
+
+
+def _spec_and_draws(rows, lstm):
+    n_layers, ndir, hid = lstm.num_layers, 2 if lstm.bidirectional else 1, lstm.hidden_size
+    p = float(lstm.dropout) if lstm.training else 0.0
+    draws = [None] * n_layers
+    if p > 0:
+        r = rng.get(rows.device)
+        for layer in range(n_layers - 1):
+            draws[layer] = r.take()
+    return (n_layers, ndir, hid, p), draws
+
+
+def sent_lstm(rows, glen, lstm):
+    """``lstm`` over the documents' sentence rows: rows [n_rows, in] laid end to end by
+    document (``glen``: rows per document, zero allowed) -> [n_rows, ndir * hid], the
+    valid rows of the reference's ``pad_packed_sequence(lstm(pack_padded_sequence(...)))``
+    (HiGraph.py:135-141).  No fallback: raises where :func:`native_lstm_ok` is false."""
+    if not native_lstm_ok(rows, lstm):
+        raise RuntimeError("sent_lstm: fp32 ROCm rows and a shape hsg_lstm_supported covers only (no fallback)")
+    lay = doc_layout(glen, rows.device)
+    if lay.n_rows != rows.shape[0]:
+        raise ValueError(f"sent_lstm: {rows.shape[0]} rows for documents of {lay.n_rows} sentences")
+    spec, draws = _spec_and_draws(rows, lstm)
+    if lay.n_rows == 0:
+        return rows.new_zeros(0, spec[1] * spec[2])
+    return _SentLSTM.apply(rows.contiguous(), lay, spec, draws, *lstm_params(lstm))
+
+
+def sent_lstm_states(rows, glen, lstm):
+    """Forward only, for tests and tools: per layer (h, c, gates, (seed, offset) or None)
+    exactly as :func:`sent_lstm` computes and saves them."""
+    if not native_lstm_ok(rows, lstm):
+        raise RuntimeError("sent_lstm_states: no native path for this call")
+    lay = doc_layout(glen, rows.device)
+    spec, draws = _spec_and_draws(rows, lstm)
+    with torch.no_grad():
+        layers = _forward(rows.contiguous(), lay, spec, [q.detach() for q in lstm_params(lstm)], draws)
+    return [(hbuf[:lay.n_rows], c, gates, draws[i]) for i, (_, _, _, hbuf, gates, c, _) in enumerate(layers)]

@@ -670,6 +670,39 @@ int hsg_cnn_pool(int n, int L, const int32_t *rowoff, const float *Y, int ldy, c
 int hsg_cnn_pool_bwd(int n, const int32_t *rowoff, const float *feat, const int32_t *arg, const float *dfeat,
                      float *dY, int lddy, void *stream);
 
+/* ---- sentence LSTM (HiGraph.py:117-123, 135-142) -------------------------------------
+ * nn.LSTM(in, hid, num_layers, bidirectional) over each document's sentence sequence,
+ * one layer per call.  Rows are the documents' sentences laid end to end: document d
+ * owns rows doc_off[d] .. doc_off[d+1]-1 (doc_off: device int32 [n_docs+1]) in time
+ * order -- no padding, no sorting; an empty document does nothing.  Direction 1 walks
+ * each document backwards.  The caller runs the input projection as one GEMM
+ * (hsg_gemm_f32): pre [n_rows][ndir*4*hid] = x W_ih^T + b_ih + b_hh, the directions'
+ * blocks side by side, torch gate order i, f, g, o.  w_hh is [ndir][4*hid][hid]
+ * (16-byte aligned).  One 4*hid-thread block runs the whole recurrence of a (document,
+ * direction) pair with its W_hh in registers; results are bitwise reproducible.
+ *   hsg_lstm_supported(hid, ndir): host-only; non-zero for the covered shapes (hid = 128,
+ *     ndir 1 or 2).  The other entry points return HSG_EINVAL elsewhere.
+ *   hsg_lstm_fwd: h_0 = c_0 = 0.  h [n_rows] rows of pitch ld_h, columns dir*hid + u (the
+ *     torch cat order); saved for the backward: gates [n_rows][ndir*4*hid] (after the
+ *     nonlinearity, columns as pre) and c [n_rows][ndir*hid] (the cell states).  With
+ *     p_drop > 0 also y (pitch ld_y) = h * keep / (1 - p), keep the FFN dropout hash
+ *     (hsg_ln_fwd's: seed[0], offset) of the element index r * (ndir*hid) + col --
+ *     nn.LSTM's inter-layer dropout; p_drop == 0: seed and y may be NULL.
+ *   hsg_lstm_bwd: the reverse-time recurrence.  dh_out (pitch ld) is the gradient with
+ *     respect to y when p_drop > 0 -- the kernel applies the forward's mask and scale
+ *     itself, given the same (p_drop, seed, offset) -- and with respect to h otherwise.
+ *     Writes dgates [n_rows][ndir*4*hid], the gradient with respect to pre; the weight
+ *     and input gradients are GEMMs on it (dX = dgates W_ih, dW_ih = dgates^T X,
+ *     dW_hh = dgates^T H_prev, db = column sums).  h_n / c_n are not produced and take
+ *     no gradient (the model discards them). */
+int hsg_lstm_supported(int hid, int ndir);
+int hsg_lstm_fwd(int n_docs, int n_rows, int hid, int ndir, const int32_t *doc_off, const float *pre, int ld_pre,
+                 const float *w_hh, float *h, int ld_h, float *gates, float *c, float p_drop, const int64_t *seed,
+                 uint32_t offset, float *y, int ld_y, void *stream);
+int hsg_lstm_bwd(int n_docs, int n_rows, int hid, int ndir, const int32_t *doc_off, const float *dh_out, int ld,
+                 const float *gates, const float *c, const float *w_hh, float p_drop, const int64_t *seed,
+                 uint32_t offset, float *dgates, void *stream);
+
 /* Library build identification (ABI version, gfx target). */
 const char *hsg_version(void);
 

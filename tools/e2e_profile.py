@@ -1,6 +1,14 @@
 """Dev tool (GPU): where the secondary end-to-end train step (bench.time_train_step)
 spends its time on cfg2 -- synchronised wall time per phase, then the same step
-under torch.profiler for the host/device split."""
+under torch.profiler for the host/device split.
+
+    python tools/e2e_profile.py [cfg] [--sent-lstm 0|1|ab] [--no-profile]
+
+--sent-lstm selects the sentence LSTM path (path_options(HSG_SENT_LSTM=...): 0 = the
+vendor nn.LSTM, 1 = the native recurrence kernels of hetersumgraph_amd.lstm).  ``ab``
+alternates the two three times in this one process and prints, per leg, one JSON line
+with the phase times plus the LSTM piece's forward and backward timed alone."""
+import json
 import os
 import sys
 import time
@@ -10,10 +18,18 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from hetersumgraph_amd import HiGraph  # noqa: E402
+from hetersumgraph_amd import _lib  # noqa: E402
 from hetersumgraph_amd import graph as hg  # noqa: E402
 
+ARGS = sys.argv[1:]
+SENT_LSTM = ARGS[ARGS.index("--sent-lstm") + 1] if "--sent-lstm" in ARGS else "0"
+if SENT_LSTM not in ("0", "1", "ab"):
+    sys.exit("--sent-lstm takes 0, 1 or ab")
+PROFILE = "--no-profile" not in ARGS and SENT_LSTM != "ab"
+POS = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] != "--sent-lstm")]
+
 dev = torch.device("cuda", 0)
-docs, G, _, _ = bench.make_shard(sys.argv[1] if len(sys.argv) > 1 else "cfg2", 0, 1, 0)
+docs, G, _, _ = bench.make_shard(POS[0] if POS else "cfg2", 0, 1, 0)
 G.to(dev)
 hps = bench._HPS(2)
 torch.manual_seed(1)
@@ -60,13 +76,61 @@ def step(n):
     G.ndata.pop("loss")
 
 
+N = 10
+
+
+def lstm_alone():
+    """(forward ms, backward ms) of the LSTM piece alone, synchronised wall time."""
+    snode_id = HiGraph.node_ids(G, "dtype", 1.0)
+    with torch.no_grad():
+        ngram, _ = model._sent_cnn_feature(G, snode_id)
+    glen = HiGraph.sentence_counts(G)
+    params = list(model.lstm.parameters()) + list(model.lstm_proj.parameters())
+    up = torch.randn(ngram.shape[0], model.lstm_proj.out_features, device=dev)
+    tf = tb = 0.0
+    for i in range(3 + N):
+        x = ngram.clone().requires_grad_()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = model._sent_lstm_rows(x, glen)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        torch.autograd.grad(out, [x] + params, up)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if i >= 3:
+            tf, tb = tf + (t1 - t0) * 1e3, tb + (t2 - t1) * 1e3
+    return tf / N, tb / N
+
+
+def leg(mode):
+    with _lib.path_options(HSG_SENT_LSTM=mode):
+        for _ in range(3):
+            step(0)
+        T.clear()
+        for _ in range(N):
+            step(0)
+        res = {k: round(v / N, 3) for k, v in T.items()}
+        res["total"] = round(sum(T.values()) / N, 3)
+        res["lstm_fwd_alone"], res["lstm_bwd_alone"] = (round(v, 3) for v in lstm_alone())
+    return res
+
+
+if SENT_LSTM == "ab":
+    for rep in range(3):
+        for mode in ("0", "1"):
+            print(json.dumps({"rep": rep, "HSG_SENT_LSTM": mode, **leg(mode)}), flush=True)
+    sys.exit(0)
+_mode = _lib.path_options(HSG_SENT_LSTM=SENT_LSTM)
+_mode.__enter__()
 for _ in range(3):
     step(0)
 T.clear()
-N = 10
 for _ in range(N):
     step(0)
 print({k: round(v / N, 3) for k, v in T.items()}, "total", round(sum(T.values()) / N, 3), flush=True)
+if not PROFILE:
+    sys.exit(0)
 from torch.profiler import ProfilerActivity, profile  # noqa: E402
 with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], with_stack=True) as prof:
     for _ in range(3):
