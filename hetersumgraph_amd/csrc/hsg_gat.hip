@@ -573,6 +573,10 @@ __global__ __launch_bounds__(256, OCC) void k_gat_fwd(RelPtrs R, int H, int D, i
                     out16[(size_t)v * ld16 + f] = (__bf16)0.f;
                 }
             }
+            if constexpr (O16) {                          // a pitch past the 64 * NF lanes' columns
+#pragma unroll 1
+                for (int f = 64 * NF + lane; f < ld16; f += 64) out16[(size_t)v * ld16 + f] = (__bf16)0.f;
+            }
             if (kact && l == 0) {
                 mout[v * H + k] = any ? mx : 0.f;
                 lout[v * H + k] = any ? sm : 1.f;
@@ -805,6 +809,10 @@ __global__ __launch_bounds__(512, 4) void k_gat_fwd_tile(RelPtrs R, int H, int D
             } else if (O16 && f < ld16) {
                 out16[(size_t)v * ld16 + f] = (__bf16)0.f;
             }
+        }
+        if constexpr (O16) {                              // a pitch past the 64 * NF lanes' columns
+#pragma unroll 1
+            for (int f = 64 * NF + lane; f < ld16; f += 64) out16[(size_t)v * ld16 + f] = (__bf16)0.f;
         }
         if (kact && l == 0) {
             mout[v * H + k] = any ? mx : 0.f;

@@ -75,8 +75,10 @@ typedef struct hsg_rel {
  *   m_v   = max(max_e s_e, 0 if phantom_v>0),  l_v = sum_e exp(s_e-m_v) + phantom_v*exp(-m_v)
  *   h[v]  = sum_e exp(s_e-m_v)/l_v * Z[src_e, k, :]      (0 if v has no in-edges)
  *   out   = origin ? elu(h) + origin : h
- * Saved for backward: h, m, l ([n_dst, H] each).  With an origin, h may be NULL (not
- * stored): the backward is then hsg_gat_bwd_dst_noh. */
+ * Saved for backward: h ([n_dst, H*D]), m, l ([n_dst, H] each); a destination without a
+ * typed in-edge, whatever its phantom count, stores m = 0, l = 1 (the backward reads m and
+ * l per typed edge only).  With an origin, h may be NULL (not stored): the backward is
+ * then hsg_gat_bwd_dst_noh. */
 int hsg_gat_fwd(const hsg_rel *rel, int H, int D, int tau_mode, float slope,
                 const float *Z, const float *sigma, const float *tau, const float *origin,
                 float *h, float *out, float *m, float *l, void *stream);
@@ -95,8 +97,10 @@ int hsg_gat_fwd_ws(const hsg_rel *rel, int H, int D, int tau_mode, float slope, 
  * (round-to-nearest-even) of pitch ld16 in out16 INSTEAD of the fp32 out (out may be
  * NULL): the bf16 GEMM mode's bf16 x rows (round 6) -- the wide FFN's A operand,
  * LayerNorm residual and dW1 operand.  ld16 % 8 == 0, ld16 >= ceil8(H*D), out16 16-byte
- * aligned; columns H*D .. ld16 - 1 are written zero (the bf16-A contract of
- * hsg_gemm_bf16_psw_io).  Per element |x16 - x| <= 2^-9 |x|. */
+ * aligned; columns H*D .. ld16 - 1 are written zero for every accepted pitch, by the
+ * whole-node epilogues and the piece merge alike (the bf16-A contract of
+ * hsg_gemm_bf16_psw_io); nothing is written past column ld16 - 1 of the last row.  Per
+ * element |x16 - x| <= 2^-9 |x|. */
 int hsg_gat_fwd_ws16(const hsg_rel *rel, int H, int D, int tau_mode, float slope, const float *Z,
                      const float *sigma, const float *tau, const float *origin, float *h, float *out, float *m,
                      float *l, float *ws, void *out16, int ld16, void *stream);
@@ -537,7 +541,9 @@ int hsg_ln_bwd_x16(int n, int d, const float *dout, const void *y, const void *x
  *                 with 16-bit resolution in p; layout, NWI = ceil(n/32),
  *                 LDC = in rounded up to 4:
  *                   bits[(k*NWI + i/32)*LDC + c] bit (i%32)
- *                 hsg_dropmask_words(n,in,H) uint32 words.
+ *                 hsg_dropmask_words(n,in,H) uint32 words, every one written; the
+ *                 bits of rows >= n in the last word and the LDC - in pad columns
+ *                 carry no meaning, and no consumer below depends on them.
  *   hsg_hproj_fwd: Z[i, kD+d]  = s * sum_c bit X[i,c] W[kD+d, c]
  *   hsg_hproj_dx:  dX[i, c]    = s * sum_k bit sum_d dZ[i, kD+d] W[kD+d, c]
  *   hsg_hproj_dw:  dW[kD+d, c] = s * sum_i dZ[i, kD+d] bit X[i,c]
@@ -635,9 +641,10 @@ int hsg_hproj_dw(int n, int in, int H, int D, const float *dZ, int ldz, const fl
  * indptr[n] / n, the piece length is P = max(min_len, mult * ceil(m)); a node with more
  * than P edges becomes ceil(deg / P) near-equal pieces, every other node one item, in
  * node order.  work holds 5 * max_items int32, max_items >= n + 2 * indptr[n] / min_len
- * + 1: the items (4 int32 each) and after them the zeroed counters; *count receives the
- * item count, or 0 when no node is longer than P (then the kernels walk the nodes as
- * before).  min_len <= 0: *count = 0.  One block; once per batch (the relation build). */
+ * + 1: the *count items (4 int32 each) and directly after them, from word 4 * *count,
+ * their *count zeroed counters -- 5 * *count words are written, the rest of work is left
+ * as it was; *count receives the item count, or 0 when no node is longer than P (then
+ * the kernels walk the nodes as before).  min_len <= 0: *count = 0.  One block; once per batch (the relation build). */
 int hsg_rel_work(int n, const int32_t *indptr, int min_len, int mult, int32_t *work, int max_items,
                  int32_t *count, void *stream);
 size_t hsg_rel_build_workspace_bytes(int n_nodes, int n_edges);

@@ -109,6 +109,26 @@ def synth_fixture(docs):
     return z
 
 
+def random_relation(rng, n_src, n_dst, max_deg, phantom_max=3, deg=None, phantom=None):
+    """A random typed relation (host arrays; .to("cuda") for the kernels) and its edge list.
+    deg / phantom: given per-destination degrees / phantom counts instead of random ones."""
+    from hetersumgraph_amd.relation import Relation
+    deg = rng.integers(0, max_deg + 1, size=n_dst) if deg is None else np.asarray(deg)
+    e_dst = np.repeat(np.arange(n_dst), deg)
+    e_src = np.concatenate([rng.choice(n_src, size=d, replace=False) if d <= n_src else
+                            rng.integers(0, n_src, size=d) for d in deg]) if deg.sum() else np.zeros(0, int)
+    tf = rng.integers(0, 11, size=len(e_dst)).astype(np.uint8)
+    phantom = rng.integers(0, phantom_max + 1, size=n_dst) if phantom is None else np.asarray(phantom)
+    indptr = np.concatenate([[0], np.cumsum(deg)])
+    corder = np.argsort(e_src, kind="stable")
+    cindptr = np.concatenate([[0], np.cumsum(np.bincount(e_src, minlength=n_src))])
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)
+    rel = Relation("W2S", n_src, n_dst, np.arange(n_src), np.arange(n_dst), i32(indptr), i32(e_src), tf,
+                   np.arange(len(e_src)), i32(phantom), i32(cindptr), i32(e_dst[corder]), i32(corder),
+                   len(e_src) + phantom.sum())
+    return rel, e_src, e_dst, tf, phantom
+
+
 def dev_lib():
     """True when the loaded library is the dev build (libhsg_dev.so via HSG_LIB_PATH):
     only it reads the A/B switches of the rejected kernel variants (csrc/hsg_dev.h);

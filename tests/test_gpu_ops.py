@@ -5,27 +5,9 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import skip_unless_dev
+from helpers import random_relation, skip_unless_dev
 
 pytestmark = pytest.mark.gpu
-
-
-def random_relation(rng, n_src, n_dst, max_deg, phantom_max=3):
-    from hetersumgraph_amd.relation import Relation
-    deg = rng.integers(0, max_deg + 1, size=n_dst)
-    e_dst = np.repeat(np.arange(n_dst), deg)
-    e_src = np.concatenate([rng.choice(n_src, size=d, replace=False) if d <= n_src else
-                            rng.integers(0, n_src, size=d) for d in deg]) if deg.sum() else np.zeros(0, int)
-    tf = rng.integers(0, 11, size=len(e_dst)).astype(np.uint8)
-    phantom = rng.integers(0, phantom_max + 1, size=n_dst)
-    indptr = np.concatenate([[0], np.cumsum(deg)])
-    corder = np.argsort(e_src, kind="stable")
-    cindptr = np.concatenate([[0], np.cumsum(np.bincount(e_src, minlength=n_src))])
-    i32 = lambda a: np.ascontiguousarray(a, np.int32)
-    rel = Relation("W2S", n_src, n_dst, np.arange(n_src), np.arange(n_dst), i32(indptr), i32(e_src), tf,
-                   np.arange(len(e_src)), i32(phantom), i32(cindptr), i32(e_dst[corder]), i32(corder),
-                   len(e_src) + phantom.sum())
-    return rel, e_src, e_dst, tf, phantom
 
 
 @pytest.mark.parametrize("H,D,max_deg,origin,per_edge", [
