@@ -63,6 +63,13 @@ def n_heads(params, prefix=""):
     return i
 
 
+def phantom_term(phantom, mx):
+    """The phantoms' share of the softmax denominator, phantom * exp(-mx), formed only
+    where there are phantoms.  There mx >= 0; a destination without phantoms whose logits
+    are all strongly negative has exp(-mx) = inf, and 0 * inf would be NaN."""
+    return torch.where(phantom > 0, phantom * torch.exp(-mx), torch.zeros_like(mx))
+
+
 def gat_heads(rel, X, params, T, prefix="", keep=None, scale=1.0):
     """Concatenated head outputs (before ELU) -- GATStackLayer.py:55-59.
     ``keep``: train mode, bool [H, n_src, in] per-head input keep-masks
@@ -91,7 +98,7 @@ def gat_heads(rel, X, params, T, prefix="", keep=None, scale=1.0):
         mx = torch.where(phantom > 0, torch.clamp_min(mx, 0.0), mx)
         mx = torch.where(torch.isinf(mx), torch.zeros_like(mx), mx).detach()
         p = torch.exp(e - mx[e_dst])
-        den = torch.zeros(n_dst, dtype=X.dtype).index_add(0, e_dst, p) + phantom * torch.exp(-mx)
+        den = torch.zeros(n_dst, dtype=X.dtype).index_add(0, e_dst, p) + phantom_term(phantom, mx)
         alpha = p / den[e_dst]
         h = torch.zeros(n_dst, D, dtype=X.dtype).index_add(0, e_dst, alpha.unsqueeze(1) * zsrc)
         outs.append(h)
@@ -173,7 +180,7 @@ def gat_aggregate_ref(e_src, e_dst, tf_row, phantom, n_dst, Z, a1, tau, origin=N
     mx = torch.where(phantom.unsqueeze(1) > 0, torch.clamp_min(mx, 0.0), mx)
     mx = torch.where(torch.isinf(mx), torch.zeros_like(mx), mx).detach()
     p = torch.exp(s - mx[e_dst])
-    den = torch.zeros(n_dst, H, dtype=Z.dtype).index_add(0, e_dst, p) + phantom.unsqueeze(1) * torch.exp(-mx)
+    den = torch.zeros(n_dst, H, dtype=Z.dtype).index_add(0, e_dst, p) + phantom_term(phantom.unsqueeze(1), mx)
     alpha = p / den[e_dst]
     h = torch.zeros(n_dst, H, D, dtype=Z.dtype).index_add(0, e_dst, alpha.unsqueeze(-1) * Zh[e_src])
     h = h.view(n_dst, H * D)

@@ -109,15 +109,16 @@ def synth_fixture(docs):
     return z
 
 
-def random_relation(rng, n_src, n_dst, max_deg, phantom_max=3, deg=None, phantom=None):
+def random_relation(rng, n_src, n_dst, max_deg, phantom_max=3, deg=None, phantom=None, tf=None):
     """A random typed relation (host arrays; .to("cuda") for the kernels) and its edge list.
-    deg / phantom: given per-destination degrees / phantom counts instead of random ones."""
+    deg / phantom: given per-destination degrees / phantom counts instead of random ones;
+    tf: given per-edge tau rows (CSR order) instead of random ones."""
     from hetersumgraph_amd.relation import Relation
     deg = rng.integers(0, max_deg + 1, size=n_dst) if deg is None else np.asarray(deg)
     e_dst = np.repeat(np.arange(n_dst), deg)
     e_src = np.concatenate([rng.choice(n_src, size=d, replace=False) if d <= n_src else
                             rng.integers(0, n_src, size=d) for d in deg]) if deg.sum() else np.zeros(0, int)
-    tf = rng.integers(0, 11, size=len(e_dst)).astype(np.uint8)
+    tf = rng.integers(0, 11, size=len(e_dst)).astype(np.uint8) if tf is None else np.ascontiguousarray(tf, np.uint8)
     phantom = rng.integers(0, phantom_max + 1, size=n_dst) if phantom is None else np.asarray(phantom)
     indptr = np.concatenate([[0], np.cumsum(deg)])
     corder = np.argsort(e_src, kind="stable")

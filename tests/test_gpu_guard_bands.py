@@ -26,14 +26,16 @@ allocates through ``mk.out`` / ``mk.inp`` / ``mk.scratch`` and returns {output n
 with a writable pointer that has no case here and no reason in its NOT_COVERED.
 """
 import ctypes
-import functools
 
 import numpy as np
 import pytest
 import torch
 
+# the edge kernels' relations, inputs and fp64 restatements: shared with test_gpu_logit_range.py
+from edge_ref import GAT_TOL, N_DST, N_SRC, SEED, ops_tol, r64, relation
+from edge_ref import gat_bwd_ref as _gat_bwd_ref
+from edge_ref import gat_fwd_inputs as _gat_fwd_inputs
 from guard import guarded, poisoned_input
-from helpers import random_relation
 
 pytestmark = pytest.mark.gpu
 
@@ -114,11 +116,6 @@ def _all_cases():
     return [pytest.param(fn, kw, id=cid) for cs in CASES.values() for cid, fn, kw in cs]
 
 
-def r64(*shape, scale=1.0):
-    """fp32-representable random values as a CPU fp32 tensor (the seeded default generator)."""
-    return torch.randn(*shape) * scale
-
-
 def P(t):
     from hetersumgraph_amd._lib import ptr
     return ptr(t)
@@ -135,36 +132,6 @@ def call(lib, name, *args):
 
 def ceil_to(x, m):
     return (x + m - 1) // m * m
-
-
-# ------------------------------------------------------------------------------------
-# relations of the edge kernels: 97 sources, 61 destinations (no multiple of 4 or of the
-# nodes per block); the LAST destination has no typed edge (phantoms only), destination 7
-# only phantoms, destination 13 no in-edge at all, destination 30 a long segment
-N_SRC, N_DST = 97, 61
-
-
-@functools.lru_cache(maxsize=None)
-def relation(kind):
-    """'short': mean segment < 16 (one wave per destination); 'long': mean >= 16 (4 waves
-    per destination); 'long_wl': 'long' with CSR / CSC work lists of a small piece length."""
-    from hetersumgraph_amd import _lib
-    rng = np.random.default_rng(61 if kind == "short" else 97)
-    if kind == "short":
-        deg = rng.integers(0, 6, size=N_DST)
-        deg[30] = 90
-    else:
-        deg = rng.integers(10, 41, size=N_DST)
-        deg[30] = 200
-    phantom = rng.integers(0, 4, size=N_DST)
-    deg[[7, 13, N_DST - 1]] = 0
-    phantom[7], phantom[13], phantom[N_DST - 1] = 3, 0, 2
-    rel, e_src, e_dst, tf, phantom = random_relation(rng, N_SRC, N_DST, 0, deg=deg, phantom=phantom)
-    with _lib.path_options(HSG_PIECE_MIN="8" if kind == "long_wl" else "0"):
-        reld = rel.to(DEV)
-    torch.cuda.synchronize()
-    assert ("dwork" in reld.dev) == (kind == "long_wl") and ("swork" in reld.dev) == (kind == "long_wl")
-    return reld, e_src, e_dst, tf, phantom
 
 
 def _work_list_post(reld, key, before):
@@ -188,38 +155,6 @@ def _work_list_post(reld, key, before):
             assert c == 0, f"{key}: counter of item {i} (no first piece) is {c}"
 
 
-def _gat_fwd_inputs(kind, H, D):
-    from oracle.fused import gat_aggregate_ref
-    reld, e_src, e_dst, tf, phantom = relation(kind)
-    HD = H * D
-    Z, a1, tau, origin = r64(N_SRC, HD), r64(H, D, scale=0.3), r64(11, H), r64(N_DST, HD)
-    sigma = (Z.double().view(N_SRC, H, D) * a1.double()).sum(-1).float()
-    h_ref = gat_aggregate_ref(e_src, e_dst, tf, phantom, N_DST, Z.double(), a1.double(), tau.double())
-    x_ref = torch.nn.functional.elu(h_ref) + origin.double()
-    return reld, Z, sigma, tau, origin, h_ref, x_ref, _ml_refs(e_src, e_dst, tf, phantom, sigma, tau, H)
-
-
-def _ml_refs(e_src, e_dst, tf, phantom, sigma, tau, H):
-    """The saved (m, l) of hsg.h in fp64: m_v = max(max_e s_e, 0 if phantom_v > 0), l_v = sum_e
-    exp(s_e - m_v) + phantom_v exp(-m_v); a destination without a typed in-edge -- phantoms
-    or not -- stores (0, 1), as hsg.h says (no edge reads them: alpha = exp(s - m) / l is per
-    typed edge).  Same tolerance as the outputs, relative to the largest entry for the sums l."""
-    es, ed, tfl = (torch.as_tensor(a).long() for a in (e_src, e_dst, tf))
-    pre = sigma.double()[es] + tau.double()[tfl]
-    s_ = torch.where(pre > 0, pre, 0.01 * pre)
-    ph = torch.as_tensor(phantom).double().unsqueeze(1)
-    m = torch.full((N_DST, H), -torch.inf, dtype=torch.float64).scatter_reduce(
-        0, ed.unsqueeze(1).expand(-1, H), s_, "amax")
-    m = torch.where(ph > 0, m.clamp_min(0.0), m)
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    l = torch.zeros(N_DST, H, dtype=torch.float64).index_add(0, ed, torch.exp(s_ - m[ed])) + ph * torch.exp(-m)
-    typed = torch.zeros(N_DST, dtype=torch.bool).index_fill(0, ed, True).unsqueeze(1)
-    m, l = torch.where(typed, m, torch.zeros_like(m)), torch.where(typed, l, torch.ones_like(l))
-    return {"m": (m, *GAT_TOL), "l": (l, GAT_TOL[0] * max(1.0, l.abs().max().item()), 0.0)}
-
-
-# tolerance of the edge forward: test_gpu_ops.py::test_gat_aggregate_matches_op_restatement (2e-5 absolute)
-GAT_TOL = (2e-5, 0.0)
 GAT_SHAPES = [dict(kind=k, H=H, D=D) for k in ("short", "long") for H, D in ((8, 8), (6, 50))]
 
 
@@ -297,60 +232,9 @@ def c_attn_src_logits(lib, mk, n, H, D):
 
 
 # ------------------------------------------------------------------------------------
-# edge backward.  The fp64 restatement is the header's formulas on the forward's fp64
-# (h, m, l); tolerance: test_gpu_ops.py::test_gat_aggregate_matches_op_restatement --
+# edge backward.  The fp64 restatement (edge_ref.gat_bwd_ref) is the header's formulas on the
+# forward's fp64 (h, m, l); tolerance: test_gpu_ops.py::test_gat_aggregate_matches_op_restatement --
 # 2e-5 * max(1, |ref|_max) per gradient.
-def _gat_bwd_ref(kind, H, D, g_bf16=False, om=1):
-    reld, e_src, e_dst, tf, phantom = relation(kind)
-    HD, E = H * D, len(e_src)
-    es, ed, tfl = torch.as_tensor(e_src).long(), torch.as_tensor(e_dst).long(), torch.as_tensor(tf).long()
-    v = dict(Z=r64(N_SRC, HD), a1=r64(H, D, scale=0.3), tau=r64(11, H), origin=r64(N_DST, HD), dout=r64(N_DST, HD))
-    Z, a1, tau = v["Z"].double(), v["a1"].double(), v["tau"].double()
-    v["sigma"] = (Z.view(N_SRC, H, D) * a1).sum(-1).float()
-    sigma = v["sigma"].double()
-    pre = sigma[es] + tau[tfl]
-    s_ = torch.where(pre > 0, pre, 0.01 * pre)
-    ph = torch.as_tensor(phantom).double().unsqueeze(1)
-    m = torch.full((N_DST, H), -torch.inf, dtype=torch.float64).scatter_reduce(
-        0, ed.unsqueeze(1).expand(-1, H), s_, "amax")
-    m = torch.where(ph > 0, m.clamp_min(0.0), m)
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    pe = torch.exp(s_ - m[ed])
-    l = torch.zeros(N_DST, H, dtype=torch.float64).index_add(0, ed, pe) + ph * torch.exp(-m)
-    l = torch.where(l == 0, torch.ones_like(l), l)          # no in-edge at all: the forward stores (0, 1)
-    alpha = pe / l[ed]                                      # [E, H]
-    Zh = Z.view(N_SRC, H, D)
-    h = torch.zeros(N_DST, H, D, dtype=torch.float64).index_add(0, ed, alpha.unsqueeze(-1) * Zh[es])
-    x = torch.nn.functional.elu(h.view(N_DST, HD)) + v["origin"].double()
-    hf = h.view(N_DST, HD)
-    G = v["dout"].double() * (torch.where(hf > 0, torch.ones_like(hf), torch.exp(hf)) if om else 1.0)   # om 0: out = h
-    if g_bf16:
-        v["G16"] = G.float().bfloat16()
-        Gu = v["G16"].double()
-    else:
-        Gu = G.float().double()                             # the G rows the kernels are handed
-    Gh = Gu.view(N_DST, H, D)
-    rho = (G.view(N_DST, H, D) * h).sum(-1)                 # G_v . h_v per head (from the fp32 G)
-    lk = torch.where(pre > 0, torch.ones_like(pre), torch.full_like(pre, 0.01))
-    dpre = alpha * ((Gh[ed] * Zh[es]).sum(-1) - rho[ed]) * lk
-    dsigma = torch.zeros(N_SRC, H, dtype=torch.float64).index_add(0, es, dpre)
-    dZ0 = torch.zeros(N_SRC, H, D, dtype=torch.float64).index_add(0, es, alpha.unsqueeze(-1) * Gh[ed])
-    dZ = (dZ0 + dsigma.unsqueeze(-1) * a1).view(N_SRC, HD)
-    dtau = torch.zeros(11, H, dtype=torch.float64).index_add(0, tfl, dpre)
-    da1 = (dsigma.unsqueeze(-1) * Zh).sum(0).view(HD)
-    r = dict(h=hf, m=m, l=l, x=x, G=G, dpre=dpre, dsigma=dsigma, dZ0=dZ0.view(N_SRC, HD), dZ=dZ, dtau=dtau.view(-1),
-             da1=da1, rho=rho)
-    # rho[v][g][s]: the 64-column-group partials of G_v . h_v, head 64 g / D + s
-    ng = (HD + 63) // 64
-    rg = torch.zeros(N_DST, ng, 3, dtype=torch.float64)
-    prod = G * hf
-    for g in range(ng if D >= 32 else 0):                   # (wide heads only: at most 3 heads per group)
-        for c in range(64 * g, min(64 * g + 64, HD)):
-            rg[:, g, c // D - (64 * g) // D] += prod[:, c]
-    r["rho_groups"] = rg
-    return reld, v, r, E
-
-
 GB = [dict(kind=k, H=H, D=D) for k in ("short", "long") for H, D in ((8, 8), (6, 50))]
 
 
@@ -476,10 +360,6 @@ def c_gat_bwd_src_g_ws(lib, mk, kind, H, D, g_bf16=0, dsig=1):
 # test_gpu_ops.py::test_gat_heads_table_matches_restatement -- 2e-5 * max(1, |ref|_max).
 LAYERS = [dict(H=8, D=8, bias=0), dict(H=6, D=50, bias=1)]
 F_TF = 50
-
-
-def ops_tol(ref):
-    return (2e-5 * max(1.0, ref.abs().max().item()), 0.0)
 
 
 def _layer_params(H, D, bias):
@@ -1802,7 +1682,7 @@ def run_case(fn, kw):
     lib = load()
     runs = []
     for guarded_mode in (True, False):
-        torch.manual_seed(20240)
+        torch.manual_seed(SEED)
         mk = Alloc(guarded_mode)
         refs = fn(lib, mk, **kw)
         torch.cuda.synchronize()
