@@ -40,6 +40,10 @@ EXPORTS = ("hsg_gat_fwd", "hsg_gat_bwd_dst", "hsg_gat_bwd_blocks", "hsg_gat_bwd_
            "hsg_gemm_bf16_psw_elug_rho_x16", "hsg_ln_fwd_x16", "hsg_ln_bwd_x16", "hsg_gemm_f32_psw_plan", "hsg_gemm_f32_psw_route",
            "hsg_lstm_supported", "hsg_lstm_fwd", "hsg_lstm_bwd")
 
+# every symbol include/hsg_train.h declares (checked by tests/test_train_abi.py)
+TRAIN_EXPORTS = ("hsg_doc_ce", "hsg_mt_tensors_per_launch", "hsg_mt_chunk", "hsg_mt_blocks", "hsg_mt_sqnorm",
+                 "hsg_mt_adam")
+
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
 HSG_EPI_ADD = 2
@@ -60,12 +64,20 @@ class HsgRel(ctypes.Structure):
                 ("dwork", ctypes.c_void_p), ("swork", ctypes.c_void_p)]
 
 
+class HsgMtTensor(ctypes.Structure):
+    """Mirror of ``struct hsg_mt_tensor`` (include/hsg_train.h)."""
+
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("n", ctypes.c_int64)]
+
+
 _lib = None
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
 _RELP = ctypes.POINTER(HsgRel)
+_MTP = ctypes.POINTER(HsgMtTensor)
 
 _SIGS = {
     "hsg_gat_fwd": [_RELP, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -166,13 +178,19 @@ _SIGS = {
     "hsg_lstm_fwd": [_I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _F, _P, ctypes.c_uint32, _P, _I, _P],
     "hsg_lstm_bwd": [_I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _F, _P, ctypes.c_uint32, _P, _P],
     "hsg_gat_bwd_src_g_ws_floats": [_RELP, _I, _I],
+    "hsg_doc_ce": [_I, _I, _I, _P, _P, _I, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P],
+    "hsg_mt_tensors_per_launch": [],
+    "hsg_mt_chunk": [],
+    "hsg_mt_blocks": [_MTP, _I],
+    "hsg_mt_sqnorm": [_MTP, _I, _P, _P, _P],
+    "hsg_mt_adam": [_MTP, _I, _P, _P, _I, _P, _P],
     "hsg_gat_bwd_src_g_ws":[_RELP, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 _RESTYPE = {"hsg_version": ctypes.c_char_p, "hsg_wsplit_dims": None, "hsg_gemm_workspace_floats": ctypes.c_size_t,
             "hsg_attn_params_bwd_workspace_floats": ctypes.c_size_t,
             "hsg_dropmask_scale": ctypes.c_float,
             "hsg_rel_build_workspace_bytes": ctypes.c_size_t, "hsg_gat_fwd_ws_floats": ctypes.c_size_t,
-            "hsg_gat_bwd_src_g_ws_floats": ctypes.c_size_t}
+            "hsg_gat_bwd_src_g_ws_floats": ctypes.c_size_t, "hsg_mt_blocks": ctypes.c_size_t}
 
 
 def load():

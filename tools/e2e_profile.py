@@ -2,12 +2,21 @@
 spends its time on cfg2 -- synchronised wall time per phase, then the same step
 under torch.profiler for the host/device split.
 
-    python tools/e2e_profile.py [cfg] [--sent-lstm 0|1|ab] [--no-profile]
+    python tools/e2e_profile.py [cfg] [--sent-lstm 0|1|ab] [--tail 0|1|ab] [--no-profile]
 
 --sent-lstm selects the sentence LSTM path (path_options(HSG_SENT_LSTM=...): 0 = the
 vendor nn.LSTM, 1 = the native recurrence kernels of hetersumgraph_amd.lstm).  ``ab``
 alternates the two three times in this one process and prints, per leg, one JSON line
-with the phase times plus the LSTM piece's forward and backward timed alone."""
+with the phase times plus the LSTM piece's forward and backward timed alone.
+
+--tail selects the step's tail (train.py:115-135 with --grad_clip at max_grad_norm = 1.0,
+phases ``loss``, ``clip``, ``adam``): 0 = torch cross entropy + sum_nodes,
+clip_grad_norm_, torch.optim.Adam with its defaults; 1 = the native tail
+(hetersumgraph_amd.loss.sentence_loss, hetersumgraph_amd.optim.Adam with the clip folded
+in, so its ``clip`` phase is empty); ``ab`` alternates leg 0, leg 1 and -- where this torch
+accepts it -- leg ``fused`` (leg 0 with torch.optim.Adam(fused=True)) three times in this
+one process, one JSON line per leg.  Without --tail the step is the one this tool always
+timed (no clipping)."""
 import json
 import os
 import sys
@@ -20,13 +29,21 @@ import bench  # noqa: E402
 from hetersumgraph_amd import HiGraph  # noqa: E402
 from hetersumgraph_amd import _lib  # noqa: E402
 from hetersumgraph_amd import graph as hg  # noqa: E402
+from hetersumgraph_amd import loss as hloss  # noqa: E402
+from hetersumgraph_amd import optim as hoptim  # noqa: E402
 
 ARGS = sys.argv[1:]
 SENT_LSTM = ARGS[ARGS.index("--sent-lstm") + 1] if "--sent-lstm" in ARGS else "0"
 if SENT_LSTM not in ("0", "1", "ab"):
     sys.exit("--sent-lstm takes 0, 1 or ab")
-PROFILE = "--no-profile" not in ARGS and SENT_LSTM != "ab"
-POS = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] != "--sent-lstm")]
+TAIL = ARGS[ARGS.index("--tail") + 1] if "--tail" in ARGS else None
+if TAIL not in (None, "0", "1", "ab"):
+    sys.exit("--tail takes 0, 1 or ab")
+if TAIL == "ab" and SENT_LSTM == "ab":
+    sys.exit("one of --sent-lstm and --tail can be ab")
+PROFILE = "--no-profile" not in ARGS and SENT_LSTM != "ab" and TAIL != "ab"
+POS = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--sent-lstm", "--tail"))]
+MAX_GRAD_NORM = 1.0
 
 dev = torch.device("cuda", 0)
 docs, G, _, _ = bench.make_shard(POS[0] if POS else "cfg2", 0, 1, 0)
@@ -36,9 +53,31 @@ torch.manual_seed(1)
 embed = torch.nn.Embedding(hps.vocab_size, 300, padding_idx=0)
 embed.weight.requires_grad = False
 model = HiGraph.HSumGraph(hps, embed).to(dev).train()
-opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=hps.lr)
+PARAMS = [p for p in model.parameters() if p.requires_grad]
+opt = torch.optim.Adam(PARAMS, lr=hps.lr)
 crit = torch.nn.CrossEntropyLoss(reduction="none")
 T = {}
+TAIL_LEG = None                  # None: the historical step; "0" / "1" / "fused": see --tail
+_TAIL_OPTS = {}
+
+
+def tail_opt(leg):
+    """One optimizer per leg over the same parameters (each keeps its own state)."""
+    if leg not in _TAIL_OPTS:
+        if leg == "1":
+            _TAIL_OPTS[leg] = hoptim.Adam(PARAMS, lr=hps.lr, max_grad_norm=MAX_GRAD_NORM)
+        else:
+            _TAIL_OPTS[leg] = torch.optim.Adam(PARAMS, lr=hps.lr, **({"fused": True} if leg == "fused" else {}))
+    return _TAIL_OPTS[leg]
+
+
+def fused_adam_ok():
+    try:
+        tail_opt("fused")
+        return True
+    except (RuntimeError, ValueError, TypeError) as e:
+        print(json.dumps({"fused_leg": "skipped", "reason": str(e)[:200]}), flush=True)
+        return False
 
 
 def tick(name, t0):
@@ -62,18 +101,27 @@ def step(n):
     st = model.gat_stack(G, w, s)
     out = model.wh(st)
     t = tick("gat_stack", t)
-    sid = G.filter_nodes(lambda nodes: nodes.data["dtype"] == 1)
-    label = G.ndata["label"][sid].sum(-1)
-    G.nodes[sid].data["loss"] = crit(out, label).unsqueeze(-1)
-    loss = hg.sum_nodes(G, "loss").mean()
+    o = opt if TAIL_LEG is None else tail_opt(TAIL_LEG)
+    if TAIL_LEG == "1":
+        loss = hloss.sentence_loss(G, out)
+    else:
+        sid = G.filter_nodes(lambda nodes: nodes.data["dtype"] == 1)
+        label = G.ndata["label"][sid].sum(-1)
+        G.nodes[sid].data["loss"] = crit(out, label).unsqueeze(-1)
+        loss = hg.sum_nodes(G, "loss").mean()
     ok = bool(torch.isfinite(loss).item())
     t = tick("loss", t)
-    opt.zero_grad()
+    o.zero_grad()
     loss.backward()
     t = tick("backward", t)
-    opt.step()
+    if TAIL_LEG in ("0", "fused"):
+        torch.nn.utils.clip_grad_norm_(PARAMS, MAX_GRAD_NORM)
+    if TAIL_LEG is not None:
+        t = tick("clip", t)              # leg 1: empty, the clip is folded into the optimizer
+    o.step()
     t = tick("adam", t)
-    G.ndata.pop("loss")
+    if TAIL_LEG != "1":
+        G.ndata.pop("loss")
 
 
 N = 10
@@ -116,6 +164,28 @@ def leg(mode):
     return res
 
 
+def tail_leg(mode):
+    global TAIL_LEG
+    TAIL_LEG = mode
+    with _lib.path_options(HSG_SENT_LSTM=SENT_LSTM):
+        for _ in range(3):
+            step(0)
+        T.clear()
+        for _ in range(N):
+            step(0)
+    res = {k: round(v / N, 3) for k, v in T.items()}
+    res["tail"] = round(sum(T[k] for k in ("loss", "clip", "adam")) / N, 3)
+    res["total"] = round(sum(T.values()) / N, 3)
+    return res
+
+
+if TAIL == "ab":
+    legs = ["0", "1"] + (["fused"] if fused_adam_ok() else [])
+    for rep_ in range(3):
+        for mode in legs:
+            print(json.dumps({"rep": rep_, "tail_leg": mode, "HSG_SENT_LSTM": SENT_LSTM, **tail_leg(mode)}), flush=True)
+    sys.exit(0)
+TAIL_LEG = TAIL
 if SENT_LSTM == "ab":
     for rep in range(3):
         for mode in ("0", "1"):
