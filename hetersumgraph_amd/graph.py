@@ -75,7 +75,13 @@ class EdgeScoreColumn(TableColumn):
     relation (an object with ``eid`` [E_T] and ``scores()`` [E_T], see
     ``module.GATLayer.LastHeadScores``) over an optional ``base`` tensor and computes the
     rows only when someone reads the column.  Values are detached (the reference's
-    column carries autograd history, which no reference caller differentiates)."""
+    column carries autograd history, which no reference caller differentiates).
+
+    Reading late must give what reading right after the forward gives: the reference's
+    column is a tensor written during the forward, so an ``optimizer.step()`` between
+    the forward and the read does not touch it.  A segment therefore OWNS what it keeps
+    -- tensors the forward produced, or copies of the parameter rows it needs, never
+    views of a live parameter (which an in-place update would change under it)."""
 
     def __init__(self, n: int, segments, base=None):
         self.n = n

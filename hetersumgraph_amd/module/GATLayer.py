@@ -181,7 +181,9 @@ def sgat_heads(g, h, params, origin=None, dropout=None):
 class SGATScores:
     """The S2S rows of ``g.edata['e']``: the last head's e = leaky(a1.z_src + a2.z_dst)
     on every dtype-0 edge (GATLayer.py:56-59, 74-75), z = 0 on words.  Formed on read,
-    like :class:`LastHeadScores`."""
+    like :class:`LastHeadScores`, from tensors the segment owns: ``Z`` is this
+    forward's product, the head's attention row is copied (a view of the parameter
+    would follow an in-place optimizer step)."""
 
     key = "S2S"
 
@@ -190,7 +192,7 @@ class SGATScores:
         H = attn.shape[0]
         D = Z.shape[1] // H
         self.z = Z.detach()[:, (H - 1) * D:]
-        self.a = attn.detach()[H - 1]
+        self.a = attn.detach()[H - 1].clone()
 
     def scores(self):
         D = self.z.shape[1]
@@ -255,29 +257,43 @@ class LastHeadScores:
     """One relation's rows of ``g.edata['e']`` (graph.EdgeScoreColumn): the last head's
     logits e = leaky_relu(a1 . z_src + a3 . feat_fc(tfidfembed)) on the typed edges
     (GATLayer.py:89-93; z_dst is the zero-initialised column there, so a2 adds
-    nothing).  Holds the application's projected features Z and the head parameters
-    (detached) and forms the rows on demand: per-edge logits are never built on the
-    HIP path.  The edge term comes from ``T`` (the [10, F] tf-idf table), ``tau_table``
-    ([11, H] per tf-idf box) or ``tau_edge`` ([E_T, H], CSR order)."""
+    nothing).  Forms the rows on demand: per-edge logits are never built on the HIP
+    path.  The source term comes from ``sigma`` ([n_src, H], the forward's own source
+    logits) or from the application's projected features ``Z`` and the head's a1; the
+    edge term from ``T`` (the [10, F] tf-idf table, with the head's a3 / feat_fc rows),
+    ``tau_table`` ([11, H] per tf-idf box) or ``tau_edge`` ([E_T, H], CSR order).
 
-    def __init__(self, kind, rel, Z, attn, wf, bf, T=None, tau_table=None, tau_edge=None):
+    The column is the FORWARD's, whatever happens to the parameters afterwards
+    (``optimizer.step()`` updates them in place; the native optimizer writes through raw
+    pointers), so the segment owns everything it keeps: ``Z``, ``sigma`` and the tau
+    tensors are products of this forward (a replay of a captured step rewrites them
+    together, so the column follows the replay), and whatever would be a view of a
+    parameter -- the head's rows of attn_fc / feat_fc and the table ``T`` -- is copied."""
+
+    def __init__(self, kind, rel, Z, attn, wf, bf, T=None, tau_table=None, tau_edge=None, sigma=None):
         self.key = kind
         d = rel.dev
         self.eid, self.src, self.tf = d["eid"], d["src"], d["tf"]
-        H = attn.shape[0]
-        D = Z.shape[1] // H
-        k = H - 1
-        self.z = Z.detach()[:, k * D:]                                   # [n_src, D]
-        self.a1 = attn.detach()[k, :D]
-        self.a3 = attn.detach()[k, 2 * D:]
-        self.wf = wf.detach()[k]                                         # [D, F]
-        self.bf = bf.detach()[k] if bf is not None else None
-        self.T = T.detach() if T is not None else None
-        self.tau_table = tau_table.detach()[:, k] if tau_table is not None else None
-        self.tau_edge = tau_edge.detach()[:, k] if tau_edge is not None else None
+        self.z = self.a1 = self.a3 = self.wf = self.bf = self.T = None
+        if sigma is not None:
+            self.sigma = sigma.detach()[:, sigma.shape[1] - 1]           # [n_src]
+        else:
+            self.sigma = None
+            H = attn.shape[0]
+            D = Z.shape[1] // H
+            k = H - 1
+            self.z = Z.detach()[:, k * D:]                               # [n_src, D]
+            self.a1 = attn.detach()[k, :D].clone()
+            if T is not None:
+                self.a3 = attn.detach()[k, 2 * D:].clone()
+                self.wf = wf.detach()[k].clone()                         # [D, F]
+                self.bf = bf.detach()[k].clone() if bf is not None else None
+                self.T = T.detach().clone()
+        self.tau_table = tau_table.detach()[:, tau_table.shape[1] - 1] if tau_table is not None else None
+        self.tau_edge = tau_edge.detach()[:, tau_edge.shape[1] - 1] if tau_edge is not None else None
 
     def scores(self):
-        sig = self.z @ self.a1                                           # [n_src]
+        sig = self.sigma if self.sigma is not None else self.z @ self.a1  # [n_src]
         if self.T is not None:
             rows = self.T @ (self.wf.t() @ self.a3)                      # [10]
             if self.bf is not None:

@@ -376,14 +376,19 @@ class _GatStack(torch.autograd.Function):
             run(s2w, rs, ("s", i + 1), ("w", i), ("w", i + 1))
             run(w2s, rw, ("w", i + 1), ("s", i + 1), ("s", i + 2))
         # g.edata['e'] as the reference leaves it: the last head's logits of the last
-        # application of each relation, formed only if someone reads the column
+        # application of each relation, formed only if someone reads the column -- from
+        # what this forward made anyway, so a late read never goes back to the
+        # parameters: the application's source logits sigma (saved[2][6]) and the tau table
+        # of its layer (saved[2][7], ops.attn_tables*: its own buffer, no view of attn_fc).
+        # No launch and no copy; an optimizer step cannot reach either tensor, and a
+        # replay of a captured step rewrites both together
         from .module.GATLayer import LastHeadScores
-        last = {lay.kind: (lay, saved) for lay, saved, *_ in apps}
+        last = {lay.kind: saved for lay, saved, *_ in apps}
         for kind in ("W2S", "S2W"):
             if kind in last:
-                lay, saved = last[kind]
-                record_edge_scores(G, LastHeadScores(kind, G.relation(kind), saved[2][0], lay.attn, lay.wf,
-                                                     lay.bf, T=T))
+                gsaved = last[kind][2]
+                record_edge_scores(G, LastHeadScores(kind, G.relation(kind), None, None, None, None,
+                                                     tau_table=gsaved[7], sigma=gsaved[6]))
         ctx.cfg, ctx.apps, ctx.bufs = cfg, apps, bufs
         ctx.params = params
         ctx.need = (w0.requires_grad, s0.requires_grad)
