@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.utils.rnn as rnn
 
-from . import _lib
+from . import _lib, head
 from .graph import TableColumn
 from .lstm import native_lstm_ok, sent_lstm
 from .module.Encoder import sentEncoder
@@ -128,8 +128,27 @@ class HSumGraph(nn.Module):
             sent_state = self.word2sent(graph, word_state, sent_state)
         return sent_state
 
+    def _glue(self, graph):
+        """Opt-in (``path_options(HSG_MODEL_GLUE="1")``): the native model glue of
+        :mod:`hetersumgraph_amd.head` where it covers the model."""
+        return (_lib.path_option("HSG_MODEL_GLUE", "0") == "1" and graph.device.type == "cuda"
+                and head.native_ok(self))
+
+    def _native_sent_feature(self, graph):
+        """``n_feature_proj(set_snfeature(graph))`` (HiGraph.py:96, 127-132, 141, 160) as one
+        native node behind the two encoders."""
+        snode_id = node_ids(graph, "dtype", 1.0)
+        ngram_feature = self.ngram_enc(graph.ndata["words"][snode_id])
+        snode_pos = graph.ndata["position"][snode_id].view(-1)
+        lstm_rows = self._sent_lstm_out(ngram_feature, sentence_counts(graph))
+        return head.sent_features(ngram_feature, snode_pos, self.sent_pos_embed.weight, lstm_rows,
+                                  self.cnn_proj, self.lstm_proj, self.n_feature_proj)
+
     def forward(self, graph):
         word_feature = self.set_wnfeature(graph)
+        if self._glue(graph):
+            sent_state = self.gat_stack(graph, word_feature, self._native_sent_feature(graph))
+            return head.sent_logits(sent_state, None, self.wh)
         sent_feature = self.n_feature_proj(self.set_snfeature(graph))
         sent_state = self.gat_stack(graph, word_feature, sent_feature)
         return self.wh(sent_state)
@@ -162,9 +181,13 @@ class HSumGraph(nn.Module):
 
         Opt-in (``path_options(HSG_SENT_LSTM="1")``): the native recurrence kernels of
         :mod:`hetersumgraph_amd.lstm` where they cover the call."""
+        return self.lstm_proj(self._sent_lstm_out(ngram, glen))
+
+    def _sent_lstm_out(self, ngram, glen):
+        """The LSTM output rows of :meth:`_sent_lstm_rows`, before ``lstm_proj``."""
         if (ngram.is_cuda and _lib.path_option("HSG_SENT_LSTM", "0") == "1"
                 and native_lstm_ok(ngram, self.lstm)):
-            return self.lstm_proj(sent_lstm(ngram, glen, self.lstm))
+            return sent_lstm(ngram, glen, self.lstm)
         n_doc, max_len = len(glen), max(glen)
         key = ("lstm_index", tuple(glen))
         idx = getattr(self, "_lstm_idx", None)
@@ -178,7 +201,7 @@ class HSumGraph(nn.Module):
         lstm_input = rnn.pack_padded_sequence(pad_seq.view(n_doc, max_len, -1), glen, batch_first=True)
         lstm_output, _ = self.lstm(lstm_input)
         unpacked, _ = rnn.pad_packed_sequence(lstm_output, batch_first=True, total_length=max_len)
-        return self.lstm_proj(unpacked.reshape(n_doc * max_len, -1).index_select(0, flat))
+        return unpacked.reshape(n_doc * max_len, -1).index_select(0, flat)
 
     def set_snfeature(self, graph):
         snode_id = node_ids(graph, "dtype", 1.0)
@@ -219,12 +242,26 @@ def _hdsg_layout(graph):
         in_s = s_rank[supers] >= 0
         pos[in_s] = s_rank[supers[in_s]]
         pos[~in_s] = len(snodes) + d_rank[supers[~in_s]]
-        return dict(pair_s=_dev(g, ps), pair_d=_dev(g, pd),
+        host = dict(pair_s=ps, pair_d=pd, n_s=len(snodes), super_pos=pos, sent_super=super_rank[snodes],
+                    doc_super=super_rank[dnodes[doc_of_sent]], inv_cnt=(1.0 / np.maximum(cnt, 1)).astype(np.float32))
+        return dict(host=host, pair_s=_dev(g, ps), pair_d=_dev(g, pd),
                     inv_cnt=_dev(g, (1.0 / np.maximum(cnt, 1)).astype(np.float32)),
                     n_docs=len(dnodes), super_pos=_dev(g, pos),
                     sent_super=_dev(g, super_rank[snodes]),
                     doc_super=_dev(g, super_rank[dnodes[doc_of_sent]]))
     return _cached(graph, "hdsg_layout", build)
+
+
+def _hdsg_head_layout(graph):
+    """The CSR / CSC forms of :func:`_hdsg_layout`'s pair list and the inverse supernode
+    lists the native glue walks (:class:`hetersumgraph_amd.head.HeadLayout`), built on the
+    host once per graph."""
+    def build():
+        lay = _hdsg_layout(graph)
+        h = lay["host"]
+        return head.HeadLayout(h["pair_s"], h["pair_d"], h["n_s"], lay["n_docs"], h["super_pos"], h["sent_super"],
+                               h["doc_super"], h["inv_cnt"], graph.device)
+    return _cached(graph, "hdsg_head_layout", build)
 
 
 class HSumDocGraph(HSumGraph):
@@ -249,6 +286,12 @@ class HSumDocGraph(HSumGraph):
     def forward(self, graph):
         lay = _hdsg_layout(graph)
         word_feature = self.set_wnfeature(graph)
+        if self._glue(graph):
+            hlay = _hdsg_head_layout(graph)
+            if hlay.ok:
+                init_state = head.doc_init(self._native_sent_feature(graph), hlay, self.dn_feature_proj)
+                super_state = self.gat_stack(graph, word_feature, init_state)
+                return head.sent_logits(super_state, hlay, self.wh)
         sent_feature = self.n_feature_proj(self.set_snfeature(graph))
         doc_feature = self.dn_feature_proj(self.set_dnfeature(graph, sent_feature))
         init_state = torch.cat([sent_feature, doc_feature], 0)[lay["super_pos"]]

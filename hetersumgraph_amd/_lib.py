@@ -44,6 +44,11 @@ EXPORTS = ("hsg_gat_fwd", "hsg_gat_bwd_dst", "hsg_gat_bwd_blocks", "hsg_gat_bwd_
 TRAIN_EXPORTS = ("hsg_doc_ce", "hsg_mt_tensors_per_launch", "hsg_mt_chunk", "hsg_mt_blocks", "hsg_mt_sqnorm",
                  "hsg_mt_adam")
 
+# every symbol include/hsg_model.h declares (checked by tests/test_model_abi.py)
+MODEL_EXPORTS = ("hsg_sentfeat_supported", "hsg_sentfeat_rows", "hsg_sentfeat_fwd", "hsg_sentfeat_bwd",
+                 "hsg_docinit_supported", "hsg_docinit_fwd", "hsg_docinit_bwd", "hsg_logits_supported",
+                 "hsg_logits_fwd", "hsg_logits_bwd_blocks", "hsg_logits_bwd")
+
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
 HSG_EPI_ADD = 2
@@ -184,6 +189,17 @@ _SIGS = {
     "hsg_mt_blocks": [_MTP, _I],
     "hsg_mt_sqnorm": [_MTP, _I, _P, _P, _P],
     "hsg_mt_adam": [_MTP, _I, _P, _P, _I, _P, _P],
+    "hsg_sentfeat_supported": [_I, _I, _I, _I],
+    "hsg_sentfeat_rows": [],
+    "hsg_sentfeat_fwd": [_I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P],
+    "hsg_sentfeat_bwd": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P],
+    "hsg_docinit_supported": [_I],
+    "hsg_docinit_fwd": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "hsg_docinit_bwd": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
+    "hsg_logits_supported": [_I],
+    "hsg_logits_fwd": [_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
+    "hsg_logits_bwd_blocks": [_I],
+    "hsg_logits_bwd": [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "hsg_gat_bwd_src_g_ws":[_RELP, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 _RESTYPE = {"hsg_version": ctypes.c_char_p, "hsg_wsplit_dims": None, "hsg_gemm_workspace_floats": ctypes.c_size_t,

@@ -2,7 +2,7 @@
 spends its time on cfg2 -- synchronised wall time per phase, then the same step
 under torch.profiler for the host/device split.
 
-    python tools/e2e_profile.py [cfg] [--sent-lstm 0|1|ab] [--tail 0|1|ab] [--no-profile]
+    python tools/e2e_profile.py [cfg] [--sent-lstm 0|1|ab] [--tail 0|1|ab] [--glue 0|1|ab] [--no-profile]
 
 --sent-lstm selects the sentence LSTM path (path_options(HSG_SENT_LSTM=...): 0 = the
 vendor nn.LSTM, 1 = the native recurrence kernels of hetersumgraph_amd.lstm).  ``ab``
@@ -16,7 +16,13 @@ clip_grad_norm_, torch.optim.Adam with its defaults; 1 = the native tail
 in, so its ``clip`` phase is empty); ``ab`` alternates leg 0, leg 1 and -- where this torch
 accepts it -- leg ``fused`` (leg 0 with torch.optim.Adam(fused=True)) three times in this
 one process, one JSON line per leg.  Without --tail the step is the one this tool always
-timed (no clipping)."""
+timed (no clipping).
+
+--glue selects the model glue (path_options(HSG_MODEL_GLUE=...): 0 = the torch ops of
+HiGraph.py, 1 = the native kernels of hetersumgraph_amd.head).  With --glue the forward is
+timed as ``model(G)`` in ONE phase, ``forward``, so both legs measure the same thing;
+``ab`` alternates leg 0 and leg 1 three times in this one process, one JSON line per leg,
+with --sent-lstm and --tail (0 or 1) applied to both."""
 import json
 import os
 import sys
@@ -39,10 +45,14 @@ if SENT_LSTM not in ("0", "1", "ab"):
 TAIL = ARGS[ARGS.index("--tail") + 1] if "--tail" in ARGS else None
 if TAIL not in (None, "0", "1", "ab"):
     sys.exit("--tail takes 0, 1 or ab")
-if TAIL == "ab" and SENT_LSTM == "ab":
-    sys.exit("one of --sent-lstm and --tail can be ab")
-PROFILE = "--no-profile" not in ARGS and SENT_LSTM != "ab" and TAIL != "ab"
-POS = [a for i, a in enumerate(ARGS) if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--sent-lstm", "--tail"))]
+GLUE = ARGS[ARGS.index("--glue") + 1] if "--glue" in ARGS else None
+if GLUE not in (None, "0", "1", "ab"):
+    sys.exit("--glue takes 0, 1 or ab")
+if [TAIL, SENT_LSTM, GLUE].count("ab") > 1:
+    sys.exit("one of --sent-lstm, --tail and --glue can be ab")
+PROFILE = "--no-profile" not in ARGS and "ab" not in (SENT_LSTM, TAIL, GLUE)
+POS = [a for i, a in enumerate(ARGS)
+       if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--sent-lstm", "--tail", "--glue"))]
 MAX_GRAD_NORM = 1.0
 
 dev = torch.device("cuda", 0)
@@ -87,8 +97,10 @@ def tick(name, t0):
     return t
 
 
-def step(n):
-    t = time.perf_counter()
+def forward_phases(t):
+    if GLUE is not None:
+        out = model(G)
+        return out, tick("forward", t)
     w = model.set_wnfeature(G)
     t = tick("set_wnfeature", t)
     snode_id = HiGraph.node_ids(G, "dtype", 1.0)
@@ -100,7 +112,11 @@ def step(n):
     s = model.n_feature_proj(torch.cat([cnn, lstm], dim=1))
     st = model.gat_stack(G, w, s)
     out = model.wh(st)
-    t = tick("gat_stack", t)
+    return out, tick("gat_stack", t)
+
+
+def step(n):
+    out, t = forward_phases(time.perf_counter())
     o = opt if TAIL_LEG is None else tail_opt(TAIL_LEG)
     if TAIL_LEG == "1":
         loss = hloss.sentence_loss(G, out)
@@ -186,12 +202,26 @@ if TAIL == "ab":
             print(json.dumps({"rep": rep_, "tail_leg": mode, "HSG_SENT_LSTM": SENT_LSTM, **tail_leg(mode)}), flush=True)
     sys.exit(0)
 TAIL_LEG = TAIL
+if GLUE == "ab":
+    for rep in range(3):
+        for mode in ("0", "1"):
+            with _lib.path_options(HSG_SENT_LSTM=SENT_LSTM, HSG_MODEL_GLUE=mode):
+                for _ in range(3):
+                    step(0)
+                T.clear()
+                for _ in range(N):
+                    step(0)
+            res = {k: round(v / N, 3) for k, v in T.items()}
+            res["total"] = round(sum(T.values()) / N, 3)
+            print(json.dumps({"rep": rep, "HSG_MODEL_GLUE": mode, "HSG_SENT_LSTM": SENT_LSTM, "tail_leg": TAIL, **res}),
+                  flush=True)
+    sys.exit(0)
 if SENT_LSTM == "ab":
     for rep in range(3):
         for mode in ("0", "1"):
             print(json.dumps({"rep": rep, "HSG_SENT_LSTM": mode, **leg(mode)}), flush=True)
     sys.exit(0)
-_mode = _lib.path_options(HSG_SENT_LSTM=SENT_LSTM)
+_mode = _lib.path_options(HSG_SENT_LSTM=SENT_LSTM, **({} if GLUE is None else {"HSG_MODEL_GLUE": GLUE}))
 _mode.__enter__()
 for _ in range(3):
     step(0)
