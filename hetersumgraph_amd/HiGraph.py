@@ -28,6 +28,7 @@ from .module.GATLayer import CHECK_NAN, TFIDF_TAG
 from .module.PositionEmbedding import get_sinusoid_encoding_table
 from .stack import fused_stack_ok
 from .stack import gat_stack as fused_gat_stack
+from .wordembed import embed_batch, native_embed_ok
 
 
 def _cached(graph, key, fn):
@@ -138,7 +139,7 @@ class HSumGraph(nn.Module):
         """``n_feature_proj(set_snfeature(graph))`` (HiGraph.py:96, 127-132, 141, 160) as one
         native node behind the two encoders."""
         snode_id = node_ids(graph, "dtype", 1.0)
-        ngram_feature = self.ngram_enc(graph.ndata["words"][snode_id])
+        ngram_feature = self._ngram(graph, snode_id)
         snode_pos = graph.ndata["position"][snode_id].view(-1)
         lstm_rows = self._sent_lstm_out(ngram_feature, sentence_counts(graph))
         return head.sent_features(ngram_feature, snode_pos, self.sent_pos_embed.weight, lstm_rows,
@@ -159,12 +160,52 @@ class HSumGraph(nn.Module):
         edges (HiGraph.py:144-152) as a table column."""
         wnode_id = node_ids(graph, "unit", 0.0)
         wid = graph.ndata["id"][wnode_id]
-        w_embed = self._embed(wid)
+        ids = self._word_embed_ids(graph)
+        if ids is not None:
+            w_embed = self._embed_both(graph, wid, ids)
+        else:
+            w_embed = self._embed(wid)
         register_tfidf_table(graph, self._TFembed.weight)
         return w_embed
 
+    # The native trainable embedding (``path_options(HSG_WORD_EMBED="1")``, INTEGRATION.md):
+    # set_wnfeature makes both lookups of the batch as one autograd node
+    # (:func:`hetersumgraph_amd.wordembed.embed_batch`) and hands the CNN's row matrix to
+    # the set_snfeature of the same forward, on the graph.  What is handed over is an
+    # activation of this forward, never kept past it: it is taken once, and only by the same
+    # model at the same version of the weights.
+    def _word_embed_ids(self, graph):
+        """The sentences' token ids when this forward takes the native embedding, else None."""
+        if not (_lib.path_option("HSG_WORD_EMBED", "0") == "1" and graph.device.type == "cuda"
+                and native_embed_ok(self._embed, self.ngram_enc)):
+            return None
+        ids = graph.ndata["words"][node_ids(graph, "dtype", 1.0)]
+        n_pos = self.ngram_enc.position_embedding.weight.shape[0]
+        if ids.dim() != 2 or ids.shape[0] == 0 or not 7 <= ids.shape[1] <= n_pos - 1:
+            return None                      # today's path states what is wrong with the batch
+        return ids
+
+    def _embed_both(self, graph, wid, ids):
+        w = self._embed.weight
+        w_embed, X, layout = embed_batch(w, wid, ids, self.ngram_enc.position_embedding.weight,
+                                         self._embed.padding_idx)
+        graph._word_embed_rows = (self, w._version, X, layout, tuple(ids.shape))
+        return w_embed
+
+    def _ngram(self, graph, snode_id):
+        """``ngram_enc`` of the sentences' token ids [n_s, 300]."""
+        held = graph.__dict__.pop("_word_embed_rows", None)
+        if held is None or held[0] is not self or held[1] != self._embed.weight._version:
+            ids = self._word_embed_ids(graph)
+            if ids is None:
+                return self.ngram_enc(graph.ndata["words"][snode_id])
+            self._embed_both(graph, ids.new_empty(0), ids)          # set_snfeature on its own
+            held = graph.__dict__.pop("_word_embed_rows")
+        _, _, X, layout, shape = held
+        return self.ngram_enc.forward_rows(X, layout, shape)
+
     def _sent_cnn_feature(self, graph, snode_id):
-        ngram_feature = self.ngram_enc(graph.ndata["words"][snode_id])           # [n_s, 300]
+        ngram_feature = self._ngram(graph, snode_id)                             # [n_s, 300]
         snode_pos = graph.ndata["position"][snode_id].view(-1)
         cnn_feature = self.cnn_proj(ngram_feature + self.sent_pos_embed(snode_pos))
         return ngram_feature, cnn_feature

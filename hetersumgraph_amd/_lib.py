@@ -49,6 +49,11 @@ MODEL_EXPORTS = ("hsg_sentfeat_supported", "hsg_sentfeat_rows", "hsg_sentfeat_fw
                  "hsg_docinit_supported", "hsg_docinit_fwd", "hsg_docinit_bwd", "hsg_logits_supported",
                  "hsg_logits_fwd", "hsg_logits_bwd_blocks", "hsg_logits_bwd")
 
+# every symbol include/hsg_embed.h declares (checked by tests/test_embed_abi.py); bound from
+# EMBED_SIGS, a table of its own next to _SIGS
+EMBED_EXPORTS = ("hsg_embed_supported", "hsg_embed_rows", "hsg_embed_keys", "hsg_embed_piece_rows", "hsg_embed_ws_floats",
+                 "hsg_embed_grad")
+
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
 HSG_EPI_ADD = 2
@@ -208,6 +213,17 @@ _RESTYPE = {"hsg_version": ctypes.c_char_p, "hsg_wsplit_dims": None, "hsg_gemm_w
             "hsg_rel_build_workspace_bytes": ctypes.c_size_t, "hsg_gat_fwd_ws_floats": ctypes.c_size_t,
             "hsg_gat_bwd_src_g_ws_floats": ctypes.c_size_t, "hsg_mt_blocks": ctypes.c_size_t}
 
+_L = ctypes.c_long
+EMBED_SIGS = {
+    "hsg_embed_supported": [_I],
+    "hsg_embed_rows": [_I, _I, _I, _P, _P, _P, _I, _P],
+    "hsg_embed_keys": [_I, _I, _I, _L, _P, _P, _P, _L, _P, _P],
+    "hsg_embed_piece_rows": [],
+    "hsg_embed_ws_floats": [_L, _I],
+    "hsg_embed_grad": [_I, _I, _L, _P, _I, _P, _I, _L, _P, _I, _P, _P, _P],
+}
+EMBED_RESTYPE = {"hsg_embed_ws_floats": ctypes.c_size_t}
+
 
 def load():
     """Load libhsg.so once; raise loudly if it is absent."""
@@ -223,6 +239,10 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPE.get(name, ctypes.c_int)
+    for name, args in EMBED_SIGS.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = EMBED_RESTYPE.get(name, ctypes.c_int)
     _lib = lib
     return lib
 

@@ -59,6 +59,31 @@ def _layout(ids):
     return length, rowoff, rows
 
 
+def _conv_pool(X, n, L, rowoff, wall, bias):
+    """Y = X Wall^T, then the shifted sum / ReLU / max-pool with argmax -> (feat, arg)."""
+    rows = X.shape[0]
+    Y = X.new_empty(rows, LDY)
+    gemm(X, wall, b_t=True, out=Y[:, :NY])
+    feat = X.new_empty(n, len(HEIGHTS) * CHANNELS)
+    arg = torch.empty(n, len(HEIGHTS) * CHANNELS, dtype=torch.int32, device=X.device)
+    bptr = (ctypes.c_void_p * len(bias))(*[b.data_ptr() for b in bias])
+    check(load().hsg_cnn_pool(n, L, ptr(rowoff), ptr(Y), LDY, bptr, ptr(feat), ptr(arg), stream_of(X)), "hsg_cnn_pool")
+    return feat, arg
+
+
+def _pool_bwd(X, n, rowoff, feat, arg, dfeat):
+    """dY [rows, LDY]: the ReLU-masked dfeat routed to the rows of each max window."""
+    dY = X.new_zeros(X.shape[0], LDY)
+    check(load().hsg_cnn_pool_bwd(n, ptr(rowoff), ptr(feat), ptr(arg), ptr(dfeat), ptr(dY), LDY, stream_of(X)),
+          "hsg_cnn_pool_bwd")
+    return dY
+
+
+def _dbias(dfeat, feat, needed):
+    masked = (dfeat * (feat > 0)).view(feat.shape[0], len(HEIGHTS), CHANNELS)
+    return [masked[:, g].sum(0) if needed[g] else None for g in range(len(HEIGHTS))]
+
+
 class _SentCNN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids, embed_w, pos_w, wall, padding_idx, *bias):
@@ -70,27 +95,18 @@ class _SentCNN(torch.autograd.Function):
         X = embed_w.new_empty(rows, D)
         check(lib.hsg_cnn_gather(n, L, D, ptr(ids), ptr(embed_w), ptr(pos_w), ptr(rowoff), rows, ptr(X), st),
               "hsg_cnn_gather")
-        Y = embed_w.new_empty(rows, LDY)
-        gemm(X, wall, b_t=True, out=Y[:, :NY])
-        feat = embed_w.new_empty(n, len(HEIGHTS) * CHANNELS)
-        arg = torch.empty(n, len(HEIGHTS) * CHANNELS, dtype=torch.int32, device=ids.device)
-        bptr = (ctypes.c_void_p * len(bias))(*[b.data_ptr() for b in bias])
-        check(lib.hsg_cnn_pool(n, L, ptr(rowoff), ptr(Y), LDY, bptr, ptr(feat), ptr(arg), st), "hsg_cnn_pool")
+        feat, arg = _conv_pool(X, n, L, rowoff, wall, bias)
         ctx.save_for_backward(ids, X, wall, rowoff, length, feat, arg)
         ctx.n_embed, ctx.padding_idx = embed_w.shape[0], padding_idx
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
-        lib = load()
         ids, X, wall, rowoff, length, feat, arg = ctx.saved_tensors
         n, L = ids.shape
         rows, D = X.shape
         dfeat = dfeat.contiguous()
-        st = stream_of(X)
-        dY = X.new_zeros(rows, LDY)
-        check(lib.hsg_cnn_pool_bwd(n, ptr(rowoff), ptr(feat), ptr(arg), ptr(dfeat), ptr(dY), LDY, st),
-              "hsg_cnn_pool_bwd")
+        dY = _pool_bwd(X, n, rowoff, feat, arg, dfeat)
         d_embed = dwall = None
         if ctx.needs_input_grad[3]:
             dwall = gemm(dY[:, :NY], X, a_t=True, splits=splits_for(NY, D, rows))
@@ -102,8 +118,7 @@ class _SentCNN(torch.autograd.Function):
             d_embed = X.new_zeros(ctx.n_embed, D).index_add_(0, tok, dX)
             if ctx.padding_idx is not None:
                 d_embed[ctx.padding_idx] = 0                  # nn.Embedding(padding_idx=...) semantics
-        masked = (dfeat * (feat > 0)).view(n, len(HEIGHTS), CHANNELS)
-        dbias = [masked[:, g].sum(0) if ctx.needs_input_grad[5 + g] else None for g in range(len(HEIGHTS))]
+        dbias = _dbias(dfeat, feat, ctx.needs_input_grad[5:])
         return (None, d_embed, None, dwall, None, *dbias)
 
 
@@ -127,3 +142,44 @@ def sent_cnn(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_i
     wall = stack_taps([w.float() for w in conv_weights])
     return _SentCNN.apply(ids.long().contiguous(), embed_weight.contiguous(), pos_weight.contiguous(), wall,
                           padding_idx, *[b.contiguous() for b in conv_biases])
+
+
+class _SentCNNRows(torch.autograd.Function):
+    """:class:`_SentCNN` behind its gather: the row matrix X is a differentiable input."""
+
+    @staticmethod
+    def forward(ctx, X, rowoff, n, L, wall, *bias):
+        feat, arg = _conv_pool(X, n, L, rowoff, wall, bias)
+        ctx.save_for_backward(X, wall, rowoff, feat, arg)
+        ctx.n = n
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        X, wall, rowoff, feat, arg = ctx.saved_tensors
+        n, D = ctx.n, X.shape[1]
+        dfeat = dfeat.contiguous()
+        dY = _pool_bwd(X, n, rowoff, feat, arg, dfeat)
+        dX = dwall = None
+        if ctx.needs_input_grad[4]:
+            dwall = gemm(dY[:, :NY], X, a_t=True, splits=splits_for(NY, D, X.shape[0]))
+        if ctx.needs_input_grad[0]:
+            dX = gemm(dY[:, :NY], wall)                                      # [rows, D]
+        return (dX, None, None, None, dwall, *_dbias(dfeat, feat, ctx.needs_input_grad[5:]))
+
+
+def sent_cnn_rows(X, layout, shape, conv_weights, conv_biases):
+    """:func:`sent_cnn` from the gathered rows on: ``X [rows, D]`` and ``layout`` as
+    :func:`hetersumgraph_amd.wordembed.embed_batch` returns them for ``ids`` of
+    ``shape = (n, L)``.  X is a differentiable input (its gradient is ``dY Wall``, computed
+    only when X requires it); the embedding gradient belongs to the node that made X."""
+    n, L = shape
+    _, rowoff, rows = layout
+    if L < max(HEIGHTS):
+        raise ValueError(f"sentEncoder: sentence length {L} < the widest kernel {max(HEIGHTS)}")
+    if X.shape[0] != rows or X.shape[1] % 4 or not X.is_contiguous():
+        raise ValueError("sentEncoder: X must be the contiguous [rows, D] row matrix of the layout, D a multiple of 4")
+    if n == 0:
+        return X.new_zeros(0, len(HEIGHTS) * CHANNELS)
+    wall = stack_taps([w.float() for w in conv_weights])
+    return _SentCNNRows.apply(X, rowoff, n, L, wall, *[b.contiguous() for b in conv_biases])

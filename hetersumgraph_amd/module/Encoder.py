@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.init as init
 
-from ..cnn import sent_cnn
+from ..cnn import sent_cnn, sent_cnn_rows
 from .PositionEmbedding import get_sinusoid_encoding_table
 
 WORD_PAD = "[PAD]"
@@ -40,3 +40,8 @@ class sentEncoder(nn.Module):
         return sent_cnn(input, self.embed.weight, self.position_embedding.weight,
                         [c.weight for c in self.convs], [c.bias for c in self.convs],
                         padding_idx=getattr(self.embed, "padding_idx", None))
+
+    def forward_rows(self, X, layout, shape):
+        """:meth:`forward` from the gathered row matrix on (``X``, ``layout`` from
+        :func:`hetersumgraph_amd.wordembed.embed_batch` for ids of ``shape``)."""
+        return sent_cnn_rows(X, layout, shape, [c.weight for c in self.convs], [c.bias for c in self.convs])

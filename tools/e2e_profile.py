@@ -2,7 +2,8 @@
 spends its time on cfg2 -- synchronised wall time per phase, then the same step
 under torch.profiler for the host/device split.
 
-    python tools/e2e_profile.py [cfg] [--sent-lstm 0|1|ab] [--tail 0|1|ab] [--glue 0|1|ab] [--no-profile]
+    python tools/e2e_profile.py [cfg] [--sent-lstm 0|1|ab] [--tail 0|1|ab] [--glue 0|1|ab]
+                                [--embed-train 0|1|ab] [--no-profile]
 
 --sent-lstm selects the sentence LSTM path (path_options(HSG_SENT_LSTM=...): 0 = the
 vendor nn.LSTM, 1 = the native recurrence kernels of hetersumgraph_amd.lstm).  ``ab``
@@ -22,7 +23,15 @@ timed (no clipping).
 HiGraph.py, 1 = the native kernels of hetersumgraph_amd.head).  With --glue the forward is
 timed as ``model(G)`` in ONE phase, ``forward``, so both legs measure the same thing;
 ``ab`` alternates leg 0 and leg 1 three times in this one process, one JSON line per leg,
-with --sent-lstm and --tail (0 or 1) applied to both."""
+with --sent-lstm and --tail (0 or 1) applied to both.
+
+--embed-train trains the word embedding (train.py:342 ``--embed_train``): the embedding's
+``requires_grad`` is set and it joins the optimizer's parameters.  0 = the torch path
+(nn.Embedding's dense backward, the CNN's index_add_ scatter, autograd's sum of the two
+[V, 300] buffers), 1 = path_options(HSG_WORD_EMBED="1"), the native node and reduce of
+hetersumgraph_amd.wordembed; ``ab`` alternates leg 0 and leg 1 three times in this one
+process, one JSON line per leg, with --sent-lstm, --tail and --glue (0 or 1) applied to
+both."""
 import json
 import os
 import sys
@@ -48,11 +57,14 @@ if TAIL not in (None, "0", "1", "ab"):
 GLUE = ARGS[ARGS.index("--glue") + 1] if "--glue" in ARGS else None
 if GLUE not in (None, "0", "1", "ab"):
     sys.exit("--glue takes 0, 1 or ab")
-if [TAIL, SENT_LSTM, GLUE].count("ab") > 1:
-    sys.exit("one of --sent-lstm, --tail and --glue can be ab")
-PROFILE = "--no-profile" not in ARGS and "ab" not in (SENT_LSTM, TAIL, GLUE)
+EMBED_TRAIN = ARGS[ARGS.index("--embed-train") + 1] if "--embed-train" in ARGS else None
+if EMBED_TRAIN not in (None, "0", "1", "ab"):
+    sys.exit("--embed-train takes 0, 1 or ab")
+if [TAIL, SENT_LSTM, GLUE, EMBED_TRAIN].count("ab") > 1:
+    sys.exit("one of --sent-lstm, --tail, --glue and --embed-train can be ab")
+PROFILE = "--no-profile" not in ARGS and "ab" not in (SENT_LSTM, TAIL, GLUE, EMBED_TRAIN)
 POS = [a for i, a in enumerate(ARGS)
-       if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--sent-lstm", "--tail", "--glue"))]
+       if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--sent-lstm", "--tail", "--glue", "--embed-train"))]
 MAX_GRAD_NORM = 1.0
 
 dev = torch.device("cuda", 0)
@@ -61,7 +73,7 @@ G.to(dev)
 hps = bench._HPS(2)
 torch.manual_seed(1)
 embed = torch.nn.Embedding(hps.vocab_size, 300, padding_idx=0)
-embed.weight.requires_grad = False
+embed.weight.requires_grad = EMBED_TRAIN is not None
 model = HiGraph.HSumGraph(hps, embed).to(dev).train()
 PARAMS = [p for p in model.parameters() if p.requires_grad]
 opt = torch.optim.Adam(PARAMS, lr=hps.lr)
@@ -216,12 +228,28 @@ if GLUE == "ab":
             print(json.dumps({"rep": rep, "HSG_MODEL_GLUE": mode, "HSG_SENT_LSTM": SENT_LSTM, "tail_leg": TAIL, **res}),
                   flush=True)
     sys.exit(0)
+if EMBED_TRAIN == "ab":
+    for rep in range(3):
+        for mode in ("0", "1"):
+            with _lib.path_options(HSG_SENT_LSTM=SENT_LSTM, HSG_WORD_EMBED=mode,
+                                   **({} if GLUE is None else {"HSG_MODEL_GLUE": GLUE})):
+                for _ in range(3):
+                    step(0)
+                T.clear()
+                for _ in range(N):
+                    step(0)
+            res = {k: round(v / N, 3) for k, v in T.items()}
+            res["total"] = round(sum(T.values()) / N, 3)
+            print(json.dumps({"rep": rep, "HSG_WORD_EMBED": mode, "HSG_SENT_LSTM": SENT_LSTM, "HSG_MODEL_GLUE": GLUE,
+                              "tail_leg": TAIL, **res}), flush=True)
+    sys.exit(0)
 if SENT_LSTM == "ab":
     for rep in range(3):
         for mode in ("0", "1"):
             print(json.dumps({"rep": rep, "HSG_SENT_LSTM": mode, **leg(mode)}), flush=True)
     sys.exit(0)
-_mode = _lib.path_options(HSG_SENT_LSTM=SENT_LSTM, **({} if GLUE is None else {"HSG_MODEL_GLUE": GLUE}))
+_mode = _lib.path_options(HSG_SENT_LSTM=SENT_LSTM, **({} if GLUE is None else {"HSG_MODEL_GLUE": GLUE}),
+                          **({} if EMBED_TRAIN is None else {"HSG_WORD_EMBED": EMBED_TRAIN}))
 _mode.__enter__()
 for _ in range(3):
     step(0)
