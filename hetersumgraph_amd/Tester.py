@@ -12,6 +12,16 @@ the top-k selection (one ``topk`` over the [docs, max_sentences] padded score
 matrix) and the match counters are batched tensor ops on the logits' device, with
 one device->host copy per batch for the selected indices; only the string work
 (n-gram blocking, hypothesis assembly) stays on the host.
+
+Opt-in (``path_options(HSG_EVAL_SELECT="1")``): the native evaluation step.  The loss is
+``hsg_doc_ce``, the selection -- n-gram blocking included -- and the match counters are one
+``hsg_eval_select`` launch (evalsel.py, include/hsg_eval.h), the loss sum and the counters
+stay in device accumulators, and the selected indices come back through pinned buffers
+behind an event, so that the host's string work for batch i-1 overlaps the device's work
+for batch i.  ``SLTester.sync()`` drains everything; the accessors call it, direct reads
+of the plain attributes (``extracts``, ``pred``, ``running_loss``...) need it first.  The
+order among EQUAL scores in that mode is include/hsg_eval.h's (ascending index), not
+torch's.
 """
 from __future__ import annotations
 
@@ -21,6 +31,7 @@ import os
 
 import torch
 
+from . import _lib
 from .HiGraph import node_ids, sentence_counts
 
 logger = logging.getLogger("Summarization logger")
@@ -127,8 +138,13 @@ class SLTester(TestPipLine):
         self._F = 0
         self.criterion = torch.nn.CrossEntropyLoss(reduction="none")
         self.blocking_win = blocking_win
+        self._pending = None                 # native path: the batch whose indices are in flight
+        self._acc = None                     # native path: device accumulators (totals int64 [4], loss fp64)
+        self._acc_dirty = False
 
     def evaluation(self, G, index, dataset, blocking=False):
+        if _lib.path_option("HSG_EVAL_SELECT", "0") == "1":
+            return self._evaluation_native(G, index, dataset, blocking)
         self.batch_number += 1
         outputs = self.model.forward(G)
         snode = node_ids(G, "dtype", 1.0)
@@ -170,7 +186,115 @@ class SLTester(TestPipLine):
             self._refer.append(example.original_abstract)
             o += N
 
+    # ---- the native evaluation step (HSG_EVAL_SELECT=1) ------------------------------------
+    def _evaluation_native(self, G, index, dataset, blocking):
+        from . import evalsel, loss
+        self.batch_number += 1
+        outputs = self.model.forward(G)
+        if not (torch.is_tensor(outputs) and outputs.is_cuda and outputs.dtype == torch.float32):
+            raise RuntimeError("SLTester (HSG_EVAL_SELECT=1): the model's logits must be fp32 on a ROCm device "
+                               "(no fallback)")
+        outputs = outputs.detach()
+        dev = outputs.device
+        counts = sentence_counts(G)
+        B = len(counts)
+        # host work while the forward runs: the examples and the n-gram ids
+        examples = [dataset.get_example(index[j]) for j in range(B)]
+        pack = None
+        if blocking and self.m != 0:
+            pack = evalsel.pack_batch([e.original_article_sents for e in examples], counts, self.blocking_win)
+        rows, labels, doc_off = loss.sentence_loss_inputs(G)
+        mean = loss.doc_cross_entropy(outputs, labels, doc_off, rows)[0]
+        if self._acc is None or self._acc[0].device != dev:
+            self.sync()
+            self._acc = (torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.float64, device=dev))
+        totals, loss_sum = self._acc
+        loss_sum.add_(mean)
+        label = labels[rows].sum(-1)                                          # [n_sent]
+        n_max = max(max(counts), 1)
+        sel_ld = n_max if self.m == 0 else min(self.m, n_max)
+        out = torch.empty(B * (sel_ld + 1 + 4), dtype=torch.int32, device=dev)
+        views = (out[:B * sel_ld].view(B, sel_ld), out[B * sel_ld:B * (sel_ld + 1)], out[B * (sel_ld + 1):].view(B, 4))
+        evalsel.select(outputs, label, doc_off, self.m, n_max, totals, None if pack is None else pack.to(dev),
+                       sel_ld, views)
+        self._acc_dirty = True
+        host = torch.empty(B * (sel_ld + 1), dtype=torch.int32, pin_memory=True)
+        host.copy_(out[:B * (sel_ld + 1)], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        prev, self._pending = self._pending, (ev, host, sel_ld, counts, examples)
+        if prev is not None:
+            self._drain(prev)
+
+    def _drain(self, pending):
+        """The host half of one batch (Tester.py:138-143), once its indices have arrived."""
+        ev, host, sel_ld, counts, examples = pending
+        ev.synchronize()
+        B = len(counts)
+        sel = host[:B * sel_ld].view(B, sel_ld).tolist()
+        nsel = host[B * sel_ld:].tolist()
+        for j in range(B):
+            if nsel[j] < 0:
+                raise RuntimeError(f"SLTester (HSG_EVAL_SELECT=1): document {j} of the batch is beyond hsg_eval_select's "
+                                   "limits or carries an invalid n-gram id")
+            pred_idx = sel[j][:nsel[j]]
+            sents = examples[j].original_article_sents
+            self.extracts.append(pred_idx)
+            self.total_sentence_num += counts[j]
+            self.example_num += 1
+            self._hyps.append("\n".join(sents[i] for i in pred_idx if i < len(sents)))
+            self._refer.append(examples[j].original_abstract)
+
+    def sync(self):
+        """Native path: drain the batch in flight and move the device accumulators into
+        ``pred / true / match_true / match`` and ``running_loss`` (one read-back).  A no-op
+        when nothing is outstanding."""
+        prev, self._pending = self._pending, None
+        if prev is not None:
+            self._drain(prev)
+        if self._acc_dirty:
+            totals, loss_sum = self._acc
+            t = totals.tolist()
+            self.running_loss += float(loss_sum)
+            totals.zero_()
+            loss_sum.zero_()
+            self._acc_dirty = False
+            self.pred += torch.tensor(t[0])
+            self.true += torch.tensor(t[1])
+            self.match_true += torch.tensor(t[2])
+            self.match += torch.tensor(t[3])
+
+    @property
+    def running_avg_loss(self):
+        self.sync()
+        return self.running_loss / self.batch_number
+
+    @property
+    def rougePairNum(self):  # noqa: N802
+        self.sync()
+        return len(self._hyps)
+
+    @property
+    def hyps(self):
+        self.sync()
+        return TestPipLine.hyps.fget(self)
+
+    @property
+    def refer(self):
+        self.sync()
+        return self._refer
+
+    @property
+    def extractLabel(self):  # noqa: N802
+        self.sync()
+        return self.extracts
+
+    def SaveDecodeFile(self):  # noqa: N802
+        self.sync()
+        super().SaveDecodeFile()
+
     def getMetric(self):  # noqa: N802
+        self.sync()
         logger.info("[INFO] Validset match_true %d, pred %d, true %d, total %d, match %d",
                     self.match_true, self.pred, self.true, self.total_sentence_num, self.match)
         self._accu, self._precision, self._recall, self._F = eval_label(

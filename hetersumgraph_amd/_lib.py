@@ -54,6 +54,10 @@ MODEL_EXPORTS = ("hsg_sentfeat_supported", "hsg_sentfeat_rows", "hsg_sentfeat_fw
 EMBED_EXPORTS = ("hsg_embed_supported", "hsg_embed_rows", "hsg_embed_keys", "hsg_embed_piece_rows", "hsg_embed_ws_floats",
                  "hsg_embed_grad")
 
+# every symbol include/hsg_eval.h declares (checked by tests/test_eval_abi.py); bound from
+# EVAL_SIGS, as EMBED_SIGS
+EVAL_EXPORTS = ("hsg_eval_select_supported", "hsg_eval_select")
+
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
 HSG_EPI_ADD = 2
@@ -223,6 +227,10 @@ EMBED_SIGS = {
     "hsg_embed_grad": [_I, _I, _L, _P, _I, _P, _I, _L, _P, _I, _P, _P, _P],
 }
 EMBED_RESTYPE = {"hsg_embed_ws_floats": ctypes.c_size_t}
+EVAL_SIGS = {
+    "hsg_eval_select_supported": [_I, _I],
+    "hsg_eval_select": [_I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P],
+}
 
 
 def load():
@@ -243,6 +251,10 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = EMBED_RESTYPE.get(name, ctypes.c_int)
+    for name, args in EVAL_SIGS.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = ctypes.c_int
     _lib = lib
     return lib
 
