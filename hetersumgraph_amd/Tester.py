@@ -22,6 +22,13 @@ for batch i.  ``SLTester.sync()`` drains everything; the accessors call it, dire
 of the plain attributes (``extracts``, ``pred``, ``running_loss``...) need it first.  The
 order among EQUAL scores in that mode is include/hsg_eval.h's (ascending index), not
 torch's.
+
+``path_options(HSG_EVAL_SELECT="words")`` is the same step with another blocking operand:
+the device takes each sentence's document-local word ids and forms the n-gram windows itself
+(``hsg_eval_select_words``, include/hsg_eval_words.h), so the host does no n-gram work.  The
+ids come from the graph when the dataset attached them in its workers
+(``ExampleSet(eval_words=True)`` -> ``G.eval_words``), else from ``evalsel.words_for``'s
+per-example cache.
 """
 from __future__ import annotations
 
@@ -143,8 +150,9 @@ class SLTester(TestPipLine):
         self._acc_dirty = False
 
     def evaluation(self, G, index, dataset, blocking=False):
-        if _lib.path_option("HSG_EVAL_SELECT", "0") == "1":
-            return self._evaluation_native(G, index, dataset, blocking)
+        mode = _lib.path_option("HSG_EVAL_SELECT", "0")
+        if mode in ("1", "words"):
+            return self._evaluation_native(G, index, dataset, blocking, mode)
         self.batch_number += 1
         outputs = self.model.forward(G)
         snode = node_ids(G, "dtype", 1.0)
@@ -186,22 +194,29 @@ class SLTester(TestPipLine):
             self._refer.append(example.original_abstract)
             o += N
 
-    # ---- the native evaluation step (HSG_EVAL_SELECT=1) ------------------------------------
-    def _evaluation_native(self, G, index, dataset, blocking):
+    # ---- the native evaluation step (HSG_EVAL_SELECT=1 or =words) --------------------------
+    def _evaluation_native(self, G, index, dataset, blocking, mode="1"):
         from . import evalsel, loss
         self.batch_number += 1
         outputs = self.model.forward(G)
         if not (torch.is_tensor(outputs) and outputs.is_cuda and outputs.dtype == torch.float32):
-            raise RuntimeError("SLTester (HSG_EVAL_SELECT=1): the model's logits must be fp32 on a ROCm device "
+            raise RuntimeError(f"SLTester (HSG_EVAL_SELECT={mode}): the model's logits must be fp32 on a ROCm device "
                                "(no fallback)")
         outputs = outputs.detach()
         dev = outputs.device
         counts = sentence_counts(G)
         B = len(counts)
-        # host work while the forward runs: the examples and the n-gram ids
+        # host work while the forward runs: the examples and the blocking operands
         examples = [dataset.get_example(index[j]) for j in range(B)]
         pack = None
-        if blocking and self.m != 0:
+        if blocking and self.m != 0 and mode == "words":
+            # word ids: from the graph if the dataset attached them, else made once per example
+            parts = getattr(G, "eval_words", None)
+            if parts is None:
+                parts = [evalsel.words_for(dataset, index[j], examples[j].original_article_sents, counts[j])
+                         for j in range(B)]
+            pack = evalsel.pack_words(parts, counts)
+        elif blocking and self.m != 0:
             pack = evalsel.pack_batch([e.original_article_sents for e in examples], counts, self.blocking_win)
         rows, labels, doc_off = loss.sentence_loss_inputs(G)
         mean = loss.doc_cross_entropy(outputs, labels, doc_off, rows)[0]
@@ -215,25 +230,32 @@ class SLTester(TestPipLine):
         sel_ld = n_max if self.m == 0 else min(self.m, n_max)
         out = torch.empty(B * (sel_ld + 1 + 4), dtype=torch.int32, device=dev)
         views = (out[:B * sel_ld].view(B, sel_ld), out[B * sel_ld:B * (sel_ld + 1)], out[B * (sel_ld + 1):].view(B, 4))
-        evalsel.select(outputs, label, doc_off, self.m, n_max, totals, None if pack is None else pack.to(dev),
-                       sel_ld, views)
+        if mode == "words":
+            evalsel.select_words(outputs, label, doc_off, self.m, n_max, self.blocking_win, totals,
+                                 None if pack is None else pack.to(dev), None, sel_ld, views)
+        else:
+            evalsel.select(outputs, label, doc_off, self.m, n_max, totals, None if pack is None else pack.to(dev),
+                           sel_ld, views)
         self._acc_dirty = True
         host = torch.empty(B * (sel_ld + 1), dtype=torch.int32, pin_memory=True)
         host.copy_(out[:B * (sel_ld + 1)], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        prev, self._pending = self._pending, (ev, host, sel_ld, counts, examples)
+        prev, self._pending = self._pending, (ev, host, sel_ld, counts, examples, mode)
         if prev is not None:
             self._drain(prev)
 
     def _drain(self, pending):
         """The host half of one batch (Tester.py:138-143), once its indices have arrived."""
-        ev, host, sel_ld, counts, examples = pending
+        ev, host, sel_ld, counts, examples, mode = pending
         ev.synchronize()
         B = len(counts)
         sel = host[:B * sel_ld].view(B, sel_ld).tolist()
         nsel = host[B * sel_ld:].tolist()
         for j in range(B):
+            if nsel[j] < 0 and mode == "words":
+                raise RuntimeError(f"SLTester (HSG_EVAL_SELECT=words): document {j} of the batch is beyond "
+                                   "hsg_eval_select_words's limits (its rows, or the windows of its chosen sentences)")
             if nsel[j] < 0:
                 raise RuntimeError(f"SLTester (HSG_EVAL_SELECT=1): document {j} of the batch is beyond hsg_eval_select's "
                                    "limits or carries an invalid n-gram id")

@@ -58,6 +58,10 @@ EMBED_EXPORTS = ("hsg_embed_supported", "hsg_embed_rows", "hsg_embed_keys", "hsg
 # EVAL_SIGS, as EMBED_SIGS
 EVAL_EXPORTS = ("hsg_eval_select_supported", "hsg_eval_select")
 
+# every symbol include/hsg_eval_words.h declares (checked by tests/test_eval_words_abi.py);
+# bound from EVALW_SIGS, as EVAL_SIGS
+EVALW_EXPORTS = ("hsg_eval_words_supported", "hsg_eval_select_words")
+
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
 HSG_EPI_ADD = 2
@@ -231,6 +235,10 @@ EVAL_SIGS = {
     "hsg_eval_select_supported": [_I, _I],
     "hsg_eval_select": [_I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P],
 }
+EVALW_SIGS = {
+    "hsg_eval_words_supported": [_I, _I, _I],
+    "hsg_eval_select_words": [_I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P],
+}
 
 
 def load():
@@ -251,10 +259,11 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = EMBED_RESTYPE.get(name, ctypes.c_int)
-    for name, args in EVAL_SIGS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = ctypes.c_int
+    for sigs in (EVAL_SIGS, EVALW_SIGS):
+        for name, args in sigs.items():
+            fn = getattr(lib, name)
+            fn.argtypes = args
+            fn.restype = ctypes.c_int
     _lib = lib
     return lib
 

@@ -660,6 +660,9 @@ def batch(graphs):
     g.batch_size = len(graphs)
     g.batch_num_nodes = [x._n for x in graphs]
     g.batch_num_edges = [len(x._src) for x in graphs]
+    # the members' word ids (ExampleSet(eval_words=True)) in member order, when every member has them
+    if graphs and all(getattr(x, "eval_words", None) is not None for x in graphs):
+        g.eval_words = [w for x in graphs for w in x.eval_words]
     return g
 
 

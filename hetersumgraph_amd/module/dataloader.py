@@ -103,8 +103,11 @@ class ExampleSet(torch.utils.data.Dataset):
     """Single-document dataset (dataloader.py:142-286); graphs built natively."""
 
     def __init__(self, data_path, vocab, doc_max_timesteps, sent_max_len, filter_word_path, w2s_path,
-                 stopwords=(), threads=1):
+                 stopwords=(), threads=1, eval_words=False):
         self.vocab = vocab
+        # opt-in: __getitem__ attaches the article's word ids to the graph (G.eval_words), the
+        # blocking operand of the native evaluation step (evalsel.word_ids, HSG_EVAL_SELECT="words")
+        self.eval_words = eval_words
         self.sent_max_len = sent_max_len
         self.doc_max_timesteps = doc_max_timesteps
         self.example_list = readJson(data_path)
@@ -136,20 +139,28 @@ class ExampleSet(torch.utils.data.Dataset):
             return np.hstack([m, np.zeros((N, self.doc_max_timesteps - k))])
         return m
 
-    def doc_item(self, index):
+    def doc_item(self, index, item=None):
         """The native builder's input for example ``index`` (see datapipe)."""
-        item = self.get_example(index)
+        item = self.get_example(index) if item is None else item
         input_pad = item.enc_sent_input_pad[:self.doc_max_timesteps]
         w2s_w = self.w2s_tfidf[index]
         return dict(sent_pad=input_pad, label=self.pad_label_m(item.label_matrix),
                     sent_tf=[tfidf_pairs(w2s_w[str(i)], self.vocab) for i in range(len(input_pad))])
 
-    def graph_arrays(self, indices):
-        return build_doc_arrays([self.doc_item(i) for i in indices], self.sent_max_len, self.filterids,
-                                threads=self.threads)
+    def graph_arrays(self, indices, items=None):
+        items = [None] * len(indices) if items is None else items
+        return build_doc_arrays([self.doc_item(i, it) for i, it in zip(indices, items)], self.sent_max_len,
+                                self.filterids, threads=self.threads)
 
     def __getitem__(self, index):
-        return to_graph(self.graph_arrays([index])[0], hg.DGLGraph), index
+        if not self.eval_words:
+            return to_graph(self.graph_arrays([index])[0], hg.DGLGraph), index
+        from ..evalsel import word_ids
+        item = self.get_example(index)
+        G = to_graph(self.graph_arrays([index], [item])[0], hg.DGLGraph)
+        rows = min(len(item.original_article_sents), self.doc_max_timesteps)      # the graph's sentence nodes
+        G.eval_words = [word_ids(item.original_article_sents, rows)]
+        return G, index
 
     def __len__(self):
         return self.size
@@ -159,9 +170,9 @@ class MultiExampleSet(ExampleSet):
     """Multi-document dataset (dataloader.py:289-423); graphs built natively."""
 
     def __init__(self, data_path, vocab, doc_max_timesteps, sent_max_len, filter_word_path, w2s_path, w2d_path,
-                 stopwords=(), threads=1):
+                 stopwords=(), threads=1, eval_words=False):
         super().__init__(data_path, vocab, doc_max_timesteps, sent_max_len, filter_word_path, w2s_path,
-                         stopwords=stopwords, threads=threads)
+                         stopwords=stopwords, threads=threads, eval_words=eval_words)
         self.w2d_tfidf = readJson(w2d_path)
 
     def get_example(self, index):
@@ -169,8 +180,8 @@ class MultiExampleSet(ExampleSet):
         e["summary"] = e.setdefault("summary", [])
         return Example2(e["text"], e["summary"], self.vocab, self.sent_max_len, e["label"])
 
-    def doc_item(self, index):
-        item = self.get_example(index)
+    def doc_item(self, index, item=None):
+        item = self.get_example(index) if item is None else item
         sent_pad = item.enc_sent_input_pad[:self.doc_max_timesteps]
         N = len(sent_pad)
         sent2doc = map_sent2doc(item.article_len, N)
@@ -182,9 +193,10 @@ class MultiExampleSet(ExampleSet):
                     art_words=[item.enc_doc_input[a] for a in range(n_art)],
                     art_tf=[tfidf_pairs(w2d_w[str(a)], self.vocab) for a in range(n_art)])
 
-    def graph_arrays(self, indices):
-        return build_doc_arrays([self.doc_item(i) for i in indices], self.sent_max_len, self.filterids,
-                                multi=True, threads=self.threads)
+    def graph_arrays(self, indices, items=None):
+        items = [None] * len(indices) if items is None else items
+        return build_doc_arrays([self.doc_item(i, it) for i, it in zip(indices, items)], self.sent_max_len,
+                                self.filterids, multi=True, threads=self.threads)
 
 
 def graph_collate_fn(samples):

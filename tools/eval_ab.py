@@ -1,7 +1,12 @@
 """A/B of the evaluation loop (GPU): SLTester.evaluation as it is by default (leg 0) against
-the native evaluation step, ``path_options(HSG_EVAL_SELECT="1")`` (leg 1).
+the native evaluation step, ``path_options(HSG_EVAL_SELECT="1")`` (leg 1), and against the
+native step on word ids, ``path_options(HSG_EVAL_SELECT="words")``, in the three states its
+host side can be in: nothing prepared, the per-example cache cleared before every batch so
+that every batch splits and interns its texts (leg 2); the ids attached to the graph, as
+``ExampleSet(eval_words=True)`` attaches them in the DataLoader workers (leg 3); the
+per-example cache warm, filled before the clock starts (leg 4).  Leg 0 is the yardstick.
 
-    python tools/eval_ab.py [--out profiles/r12_eval/eval_ab.jsonl] [--batches 20] [--rounds 3]
+    python tools/eval_ab.py [--out profiles/r13_eval_words/eval_ab.jsonl] [--batches 20] [--rounds 3]
 
 One process, one device.  A cfg2-shaped batch (32 documents of 35 sentences), the real
 HSumGraph forward in eval mode with random-init weights, synthetic article texts, m = 3 with
@@ -9,8 +14,9 @@ n-gram blocking on.  After a warm-up of both legs the legs alternate ``--rounds`
 each run is ``--batches`` evaluation calls on a fresh tester and is timed with a host clock
 from the first call to the end of the closing ``getMetric()`` (which, on leg 1, is the final
 ``sync()``) followed by a device synchronise.  Every run is printed and written as one JSON
-line -- none is dropped or picked -- followed by one line with the host cost of the n-gram
-packing alone and one that states whether the two legs selected the same sentences.
+line -- none is dropped or picked -- followed by lines with the host cost of the operand
+packing alone (n-gram ids; word ids made from the texts; word ids already made) and one that
+states whether all legs selected the same sentences.
 """
 import argparse
 import json
@@ -73,7 +79,7 @@ def make_articles(rng, counts, vocab=3000, phrases=40):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "r12_eval", "eval_ab.jsonl"))
+    ap.add_argument("--out", default=os.path.join("profiles", "r13_eval_words", "eval_ab.jsonl"))
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=3)
@@ -93,12 +99,29 @@ def main():
     embed = torch.nn.Embedding(hps.vocab_size, hps.word_emb_dim, padding_idx=0)
     model = HiGraph.HSumGraph(hps, embed).to(dev).eval()
 
+    sents = [e.original_article_sents for e in data.examples]
+    attached = [evalsel.word_ids(s, c) for s, c in zip(sents, counts)]
+    LEGS = {0: ("0", "default"), 1: ("1", "HSG_EVAL_SELECT=1"),
+            2: ("words", "HSG_EVAL_SELECT=words, nothing prepared (cache cleared before every batch)"),
+            3: ("words", "HSG_EVAL_SELECT=words, G.eval_words attached"),
+            4: ("words", "HSG_EVAL_SELECT=words, warm per-example cache")}
+
     def run(leg, batches):
         t = SLTester(model, 3, limited=False, blocking_win=3)
-        with torch.no_grad(), _lib.path_options(HSG_EVAL_SELECT=str(leg)):
+        if leg == 3:
+            G.eval_words = attached
+        elif hasattr(G, "eval_words"):
+            del G.eval_words
+        evalsel.clear_word_cache()
+        if leg == 4:                                       # warm: filled before the clock starts
+            for j, c in zip(index, counts):
+                evalsel.words_for(data, j, data.get_example(j).original_article_sents, c)
+        with torch.no_grad(), _lib.path_options(HSG_EVAL_SELECT=LEGS[leg][0]):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(batches):
+                if leg == 2:
+                    evalsel.clear_word_cache()
                 t.evaluation(G, index, data, blocking=True)
             t.getMetric()
             torch.cuda.synchronize()
@@ -111,26 +134,36 @@ def main():
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
 
-    for leg in (0, 1):
+    for leg in LEGS:
         run(leg, args.warmup)
     testers = {}
     for rnd in range(args.rounds):
-        for leg in (0, 1):
+        for leg in LEGS:
             t, dt = run(leg, args.batches)
             testers[leg] = t
-            emit({"round": rnd, "leg": leg, "path": "default" if leg == 0 else "HSG_EVAL_SELECT=1",
+            emit({"round": rnd, "leg": leg, "path": LEGS[leg][1],
                   "batches": args.batches, "docs_per_batch": len(counts), "sentences_per_batch": sum(counts),
                   "ms_per_batch": round(dt / args.batches * 1e3, 3)})
-    sents = [e.original_article_sents for e in data.examples]
     t0 = time.perf_counter()
     for _ in range(args.batches):
         pack = evalsel.pack_batch(sents, counts, 3)
     emit({"host_only": "evalsel.pack_batch", "ms_per_batch": round((time.perf_counter() - t0) / args.batches * 1e3, 3),
           "ngram_ids_per_batch": pack.T, "gram_max": pack.gram_max})
-    a, b = testers[0], testers[1]
-    emit({"same_extracts": a.extracts == b.extracts, "same_counters": all(
-        int(getattr(a, k)) == int(getattr(b, k)) for k in ("pred", "true", "match", "match_true")),
-          "running_loss": [float(a.running_loss), float(b.running_loss)],
+    t0 = time.perf_counter()
+    for _ in range(args.batches):
+        words = evalsel.pack_words([evalsel.word_ids(s, c) for s, c in zip(sents, counts)], counts)
+    emit({"host_only": "evalsel.word_ids + pack_words", "words_per_batch": words.W, "tab_cap": words.tab_cap(3, 3),
+          "ms_per_batch": round((time.perf_counter() - t0) / args.batches * 1e3, 3)})
+    t0 = time.perf_counter()
+    for _ in range(args.batches):
+        words = evalsel.pack_words(attached, counts)
+        words.tab_cap(3, 3)
+    emit({"host_only": "evalsel.pack_words + tab_cap (ids already made)",
+          "ms_per_batch": round((time.perf_counter() - t0) / args.batches * 1e3, 3)})
+    a = testers[0]
+    emit({"same_extracts": all(a.extracts == b.extracts for b in testers.values()), "same_counters": all(
+        int(getattr(a, k)) == int(getattr(b, k)) for b in testers.values() for k in ("pred", "true", "match", "match_true")),
+          "running_loss": [float(b.running_loss) for b in testers.values()],
           "device": torch.cuda.get_device_name(0), "lib": _lib.version()})
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
