@@ -29,6 +29,13 @@ the device takes each sentence's document-local word ids and forms the n-gram wi
 ids come from the graph when the dataset attached them in its workers
 (``ExampleSet(eval_words=True)`` -> ``G.eval_words``), else from ``evalsel.words_for``'s
 per-example cache.
+
+``path_options(HSG_EVAL_SELECT="text")`` is that step with the word ids made on the device: the
+host encodes the article sentences and hands over their bytes (``evalsel.pack_text``), the
+device splits them at ``str.split()``'s whitespace and interns the words
+(``hsg_eval_text_words``, include/hsg_eval_text.h), and the unchanged ``hsg_eval_select_words``
+selects.  Ids attached to the graph are used as they are; the per-example cache is neither
+read nor filled.
 """
 from __future__ import annotations
 
@@ -151,7 +158,7 @@ class SLTester(TestPipLine):
 
     def evaluation(self, G, index, dataset, blocking=False):
         mode = _lib.path_option("HSG_EVAL_SELECT", "0")
-        if mode in ("1", "words"):
+        if mode in ("1", "words", "text"):
             return self._evaluation_native(G, index, dataset, blocking, mode)
         self.batch_number += 1
         outputs = self.model.forward(G)
@@ -194,7 +201,7 @@ class SLTester(TestPipLine):
             self._refer.append(example.original_abstract)
             o += N
 
-    # ---- the native evaluation step (HSG_EVAL_SELECT=1 or =words) --------------------------
+    # ---- the native evaluation step (HSG_EVAL_SELECT=1, =words or =text) -------------------
     def _evaluation_native(self, G, index, dataset, blocking, mode="1"):
         from . import evalsel, loss
         self.batch_number += 1
@@ -208,14 +215,18 @@ class SLTester(TestPipLine):
         B = len(counts)
         # host work while the forward runs: the examples and the blocking operands
         examples = [dataset.get_example(index[j]) for j in range(B)]
-        pack = None
-        if blocking and self.m != 0 and mode == "words":
-            # word ids: from the graph if the dataset attached them, else made once per example
+        pack = text = None
+        if blocking and self.m != 0 and mode in ("words", "text"):
+            # word ids: from the graph if the dataset attached them; else made once per example
+            # ("words"), or made on the device from the sentences' bytes ("text")
             parts = getattr(G, "eval_words", None)
-            if parts is None:
-                parts = [evalsel.words_for(dataset, index[j], examples[j].original_article_sents, counts[j])
-                         for j in range(B)]
-            pack = evalsel.pack_words(parts, counts)
+            if parts is None and mode == "text":
+                text = evalsel.pack_text([e.original_article_sents for e in examples], counts)
+            else:
+                if parts is None:
+                    parts = [evalsel.words_for(dataset, index[j], examples[j].original_article_sents, counts[j])
+                             for j in range(B)]
+                pack = evalsel.pack_words(parts, counts)
         elif blocking and self.m != 0:
             pack = evalsel.pack_batch([e.original_article_sents for e in examples], counts, self.blocking_win)
         rows, labels, doc_off = loss.sentence_loss_inputs(G)
@@ -230,7 +241,11 @@ class SLTester(TestPipLine):
         sel_ld = n_max if self.m == 0 else min(self.m, n_max)
         out = torch.empty(B * (sel_ld + 1 + 4), dtype=torch.int32, device=dev)
         views = (out[:B * sel_ld].view(B, sel_ld), out[B * sel_ld:B * (sel_ld + 1)], out[B * (sel_ld + 1):].view(B, 4))
-        if mode == "words":
+        if text is not None:
+            evalsel.select_words(outputs, label, doc_off, self.m, n_max, self.blocking_win, totals,
+                                 evalsel.text_words(text.to(dev), doc_off), text.tab_cap(self.blocking_win, self.m),
+                                 sel_ld, views)
+        elif mode in ("words", "text"):
             evalsel.select_words(outputs, label, doc_off, self.m, n_max, self.blocking_win, totals,
                                  None if pack is None else pack.to(dev), None, sel_ld, views)
         else:
@@ -253,8 +268,8 @@ class SLTester(TestPipLine):
         sel = host[:B * sel_ld].view(B, sel_ld).tolist()
         nsel = host[B * sel_ld:].tolist()
         for j in range(B):
-            if nsel[j] < 0 and mode == "words":
-                raise RuntimeError(f"SLTester (HSG_EVAL_SELECT=words): document {j} of the batch is beyond "
+            if nsel[j] < 0 and mode in ("words", "text"):
+                raise RuntimeError(f"SLTester (HSG_EVAL_SELECT={mode}): document {j} of the batch is beyond "
                                    "hsg_eval_select_words's limits (its rows, or the windows of its chosen sentences)")
             if nsel[j] < 0:
                 raise RuntimeError(f"SLTester (HSG_EVAL_SELECT=1): document {j} of the batch is beyond hsg_eval_select's "

@@ -62,6 +62,11 @@ EVAL_EXPORTS = ("hsg_eval_select_supported", "hsg_eval_select")
 # bound from EVALW_SIGS, as EVAL_SIGS
 EVALW_EXPORTS = ("hsg_eval_words_supported", "hsg_eval_select_words")
 
+# every symbol include/hsg_eval_text.h declares (checked by tests/test_eval_text_abi.py);
+# bound from EVALT_SIGS / EVALT_RESTYPE, as EMBED_SIGS
+EVALT_EXPORTS = ("hsg_eval_text_supported", "hsg_eval_text_word_bound", "hsg_eval_text_workspace_bytes",
+                 "hsg_eval_text_words")
+
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
 HSG_EPI_ADD = 2
@@ -239,6 +244,14 @@ EVALW_SIGS = {
     "hsg_eval_words_supported": [_I, _I, _I],
     "hsg_eval_select_words": [_I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P],
 }
+_L64 = ctypes.c_int64
+EVALT_SIGS = {
+    "hsg_eval_text_supported": [_I, _I, _L64],
+    "hsg_eval_text_word_bound": [_I, _L64],
+    "hsg_eval_text_workspace_bytes": [_I, _I, _L64],
+    "hsg_eval_text_words": [_I, _I, _P, _L64, _P, _P, _L64, _P, _P, _P, _P],
+}
+EVALT_RESTYPE = {"hsg_eval_text_word_bound": ctypes.c_int64, "hsg_eval_text_workspace_bytes": ctypes.c_size_t}
 
 
 def load():
@@ -264,6 +277,10 @@ def load():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = ctypes.c_int
+    for name, args in EVALT_SIGS.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = EVALT_RESTYPE.get(name, ctypes.c_int)
     _lib = lib
     return lib
 

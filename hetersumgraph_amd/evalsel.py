@@ -14,6 +14,10 @@ of ``hsg_eval_select_supported``, raise ``RuntimeError``.
 The second half of the module is the same selection with blocking on WORD ids
 (``hsg_eval_select_words``, include/hsg_eval_words.h): :func:`word_ids`, :func:`pack_words`,
 :func:`select_words` and the per-example cache :func:`words_for`.
+
+The last part makes those word ids on the device from the sentences' UTF-8 bytes
+(``hsg_eval_text_words``, include/hsg_eval_text.h): :func:`pack_text` and :func:`text_words`.
+The host encodes and concatenates; it neither splits nor interns.
 """
 from __future__ import annotations
 
@@ -198,6 +202,7 @@ class WordPack:
     def win_need(self, n_win, m):
         """The most windows a document of the batch can have stored: over the documents, the
         largest sum of the min(m, N_d) largest per-sentence window counts (with repeats)."""
+        _require(self.lens is not None, "a word pack made on the device has no word counts on the host: pass tab_cap")
         win = np.maximum(self.lens - int(n_win), 0)
         need, o = 0, 0
         for c in self.counts:
@@ -322,3 +327,104 @@ def words_for(dataset, index, sents, n_rows):
 def clear_word_cache():
     """Drop every cached word-id list (after a dataset's texts were changed in place)."""
     _WORD_CACHE.clear()
+
+
+# ---- word ids from the sentences' bytes (C ABI: hsg_eval_text_words, include/hsg_eval_text.h) --
+# Equal words are equal UTF-8 byte strings and the selection only compares ids with each other,
+# so the device can split at str.split()'s whitespace and intern by itself.  The host's part is
+# one encode per sentence and one join.
+
+TAB_CAP_MAX = 8192                                         # hsg_eval_words_supported's largest table
+
+
+class TextPack:
+    """One batch's article bytes in ONE uint8 buffer: [byte_ptr (n + 1) int32 | the rows' bytes].
+    ``lens`` (bytes per row) and ``counts`` (rows per document) stay on the host for
+    :meth:`tab_cap`."""
+
+    def __init__(self, buf, n, B, nbytes, lens, counts):
+        self.buf, self.n, self.B, self.nbytes, self.lens, self.counts = buf, n, B, nbytes, lens, counts
+
+    def views(self, buf=None):
+        """(byte_ptr int32 [n + 1], text uint8 [nbytes]) as views of ``buf`` (default: this pack's)."""
+        buf = self.buf if buf is None else buf
+        head = 4 * (self.n + 1)
+        return buf[:head].view(torch.int32), buf[head:]
+
+    def to(self, device):
+        """The device copy (one non-blocking copy when the host buffer is pinned)."""
+        return TextPack(self.buf.to(device, non_blocking=True), self.n, self.B, self.nbytes, self.lens, self.counts)
+
+    def word_bound(self):
+        """Per row, the most words its bytes can hold: ceil(L / 2)."""
+        return (self.lens + 1) // 2
+
+    def tab_cap(self, n_win, m):
+        """Slots of the device's seen set for this batch: :meth:`WordPack.tab_cap`'s rule on the
+        per-row bound ceil(L / 2) instead of the true word counts (nobody has counted the
+        words), clamped to the kernel's largest table.  A document whose chosen sentences
+        really store more windows than that is refused by the kernel, as documented there."""
+        cap = WordPack(None, self.n, self.B, 0, self.word_bound(), self.counts).tab_cap(n_win, m)
+        return min(cap, TAB_CAP_MAX)
+
+
+def pack_text(list_of_sents, counts, pin=None):
+    """:class:`TextPack` of a batch: ``list_of_sents[d]`` are document d's article sentences,
+    ``counts[d]`` its number of sentence nodes.  Only the first ``counts[d]`` sentences are
+    taken and rows beyond the article are empty (:func:`word_ids`' rule).  A sentence is
+    encoded with ``encode("utf-8", "surrogatepass")``, under which every ``str`` has bytes and
+    equal bytes <=> equal ``str``.  The buffer is pinned when a GPU is present (``pin``)."""
+    counts = [int(c) for c in counts]
+    B, n = len(counts), sum(counts)
+    _require(len(list_of_sents) == B, "texts and sentence counts are of different batches")
+    lens = np.zeros(n, np.int64)
+    encs, row = [], 0
+    for sents, c in zip(list_of_sents, counts):
+        e = [s.encode("utf-8", "surrogatepass") for s in sents[:c]]
+        lens[row:row + len(e)] = [len(x) for x in e]
+        encs += e
+        row += c
+    nbytes = int(lens.sum())
+    _require(nbytes < 2 ** 31, "more than 2^31 bytes of text in one batch")
+    pin = torch.cuda.is_available() if pin is None else pin
+    head = 4 * (n + 1)
+    buf = torch.empty(head + nbytes, dtype=torch.uint8, pin_memory=pin)
+    a = buf.numpy()
+    p = a[:head].view(np.int32)
+    p[0] = 0
+    np.cumsum(lens, out=p[1:])
+    a[head:] = np.frombuffer(b"".join(encs), np.uint8)
+    return TextPack(buf, n, B, nbytes, lens, counts)
+
+
+def text_supported(n, B, nbytes):
+    return bool(load().hsg_eval_text_supported(int(n), int(B), int(nbytes)))
+
+
+def text_words(pack, doc_off=None):
+    """``hsg_eval_text_words`` on a device :class:`TextPack`: a device :class:`WordPack` (one
+    int32 buffer [word_ptr | word_ids], ``lens = None``) for :func:`select_words`, which then
+    needs an explicit ``tab_cap`` (:meth:`TextPack.tab_cap`).  ``doc_off``: the batch's int32
+    [B + 1] on the pack's device (default: made from the pack's counts).  Nothing here waits
+    for the device."""
+    _require(isinstance(pack, TextPack) and torch.is_tensor(pack.buf) and pack.buf.is_cuda
+             and pack.buf.dtype == torch.uint8 and pack.buf.is_contiguous(),
+             "the text pack must be uint8 on a ROCm device")
+    dev, n, B, nbytes = pack.buf.device, pack.n, pack.B, pack.nbytes
+    _require(pack.buf.numel() == 4 * (n + 1) + nbytes, "the text pack's buffer is of another batch")
+    _require(text_supported(n, B, nbytes),
+             f"n {n} / B {B} / nbytes {nbytes} beyond hsg_eval_text_supported (0..2^20 rows, 1..2^20 documents, "
+             "0..2^30 bytes)")
+    if doc_off is None:
+        doc_off = torch.tensor(np.concatenate([[0], np.cumsum(pack.counts)]), dtype=torch.int32).to(dev)
+    _require(torch.is_tensor(doc_off) and doc_off.device == dev and doc_off.dtype == torch.int32
+             and doc_off.is_contiguous() and doc_off.shape == (B + 1,),
+             "doc_off must be contiguous int32 [B + 1] on the pack's device")
+    lib = load()
+    cap = int(lib.hsg_eval_text_word_bound(n, nbytes))
+    out = torch.empty(n + 1 + max(cap, 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.hsg_eval_text_workspace_bytes(n, B, nbytes)), dtype=torch.uint8, device=dev)
+    byte_ptr, text = pack.views()
+    check(lib.hsg_eval_text_words(n, B, ptr(text) if nbytes else None, nbytes, ptr(byte_ptr), ptr(doc_off), cap,
+                                  ptr(out), ptr(out[n + 1:]), ptr(ws), stream_of(out)), "hsg_eval_text_words")
+    return WordPack(out, n, B, cap, None, pack.counts)

@@ -4,9 +4,12 @@ native step on word ids, ``path_options(HSG_EVAL_SELECT="words")``, in the three
 host side can be in: nothing prepared, the per-example cache cleared before every batch so
 that every batch splits and interns its texts (leg 2); the ids attached to the graph, as
 ``ExampleSet(eval_words=True)`` attaches them in the DataLoader workers (leg 3); the
-per-example cache warm, filled before the clock starts (leg 4).  Leg 0 is the yardstick.
+per-example cache warm, filled before the clock starts (leg 4).  Leg 5 is the native step with
+the word ids made on the device from the sentences' bytes,
+``path_options(HSG_EVAL_SELECT="text")``, with nothing prepared and the cache cleared before
+every batch, as leg 2.  Leg 0 is the yardstick.
 
-    python tools/eval_ab.py [--out profiles/r13_eval_words/eval_ab.jsonl] [--batches 20] [--rounds 3]
+    python tools/eval_ab.py [--out profiles/r14_eval_text/eval_ab.jsonl] [--batches 20] [--rounds 3]
 
 One process, one device.  A cfg2-shaped batch (32 documents of 35 sentences), the real
 HSumGraph forward in eval mode with random-init weights, synthetic article texts, m = 3 with
@@ -15,8 +18,8 @@ each run is ``--batches`` evaluation calls on a fresh tester and is timed with a
 from the first call to the end of the closing ``getMetric()`` (which, on leg 1, is the final
 ``sync()``) followed by a device synchronise.  Every run is printed and written as one JSON
 line -- none is dropped or picked -- followed by lines with the host cost of the operand
-packing alone (n-gram ids; word ids made from the texts; word ids already made) and one that
-states whether all legs selected the same sentences.
+packing alone (n-gram ids; word ids made from the texts; word ids already made; the texts'
+bytes) and one that states whether all legs selected the same sentences.
 """
 import argparse
 import json
@@ -79,7 +82,7 @@ def make_articles(rng, counts, vocab=3000, phrases=40):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "r13_eval_words", "eval_ab.jsonl"))
+    ap.add_argument("--out", default=os.path.join("profiles", "r14_eval_text", "eval_ab.jsonl"))
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=3)
@@ -104,7 +107,8 @@ def main():
     LEGS = {0: ("0", "default"), 1: ("1", "HSG_EVAL_SELECT=1"),
             2: ("words", "HSG_EVAL_SELECT=words, nothing prepared (cache cleared before every batch)"),
             3: ("words", "HSG_EVAL_SELECT=words, G.eval_words attached"),
-            4: ("words", "HSG_EVAL_SELECT=words, warm per-example cache")}
+            4: ("words", "HSG_EVAL_SELECT=words, warm per-example cache"),
+            5: ("text", "HSG_EVAL_SELECT=text, nothing prepared (cache cleared before every batch)")}
 
     def run(leg, batches):
         t = SLTester(model, 3, limited=False, blocking_win=3)
@@ -120,7 +124,7 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(batches):
-                if leg == 2:
+                if leg in (2, 5):
                     evalsel.clear_word_cache()
                 t.evaluation(G, index, data, blocking=True)
             t.getMetric()
@@ -159,6 +163,13 @@ def main():
         words = evalsel.pack_words(attached, counts)
         words.tab_cap(3, 3)
     emit({"host_only": "evalsel.pack_words + tab_cap (ids already made)",
+          "ms_per_batch": round((time.perf_counter() - t0) / args.batches * 1e3, 3)})
+    t0 = time.perf_counter()
+    for _ in range(args.batches):
+        text = evalsel.pack_text(sents, counts)
+        text.tab_cap(3, 3)
+    emit({"host_only": "evalsel.pack_text + tab_cap", "bytes_per_batch": text.nbytes, "tab_cap": text.tab_cap(3, 3),
+          "word_bound": int(text.word_bound().sum()),
           "ms_per_batch": round((time.perf_counter() - t0) / args.batches * 1e3, 3)})
     a = testers[0]
     emit({"same_extracts": all(a.extracts == b.extracts for b in testers.values()), "same_counters": all(
