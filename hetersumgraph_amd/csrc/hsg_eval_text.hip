@@ -1,5 +1,5 @@
 // hsg_eval_text.hip -- document-local word ids from the sentences' UTF-8 bytes, for gfx950: the
-// blocking operand of hsg_eval_select_words (hsg_eval_words.hip) made on the device, so that
+// blocking operand of hsg_eval_select_words (hsg_eval.hip) made on the device, so that
 // the host neither splits nor interns.  C ABI and the whole contract: include/hsg_eval_text.h.
 //
 //   k_text_count   one wave per row.  Lane j of a stride looks at byte p = lo + base + j: a

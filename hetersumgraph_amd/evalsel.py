@@ -1,5 +1,5 @@
 """Evaluation-time sentence selection on the native kernel (C ABI: hsg_eval_select,
-include/hsg_eval.h, csrc/hsg_eval.hip).
+include/hsg_eval.h, csrc/hsg_eval.hip: the one file of both selection kernels).
 
 Reference: ``SLTester.evaluation`` (Tester.py:105-140) and ``ngram_blocking``
 (Tester.py:155-184).  The device does the candidate order, the top-m walk with or without
@@ -105,16 +105,10 @@ def pack_batch(list_of_sents, counts, n_win, pin=None):
     return GramPack(buf, n, B, T, max([p[2] for p in parts], default=0))
 
 
-def supported(n_max, gram_max=0):
-    return bool(load().hsg_eval_select_supported(int(n_max), int(gram_max)))
-
-
-def select(logits, labels, doc_off, m, n_max, totals, grams=None, sel_ld=None, out=None):
-    """``hsg_eval_select`` on device tensors: returns (sel int32 [B, sel_ld], nsel int32 [B],
-    doc_counts int32 [B, 4]) and adds the batch's counters into ``totals`` (int64 [4], on the
-    device, accumulated).  ``grams``: a device :class:`GramPack` for n-gram blocking, or
-    None.  ``out``: optional (sel, nsel, doc_counts) to write into.  Nothing here waits for
-    the device."""
+def _batch(logits, labels, doc_off, m, n_max, totals, sel_ld, out):
+    """What :func:`select` and :func:`select_words` share: the checks of the batch's tensors,
+    the ``sel_ld`` rule and the outputs, allocated unless given.  Returns (logits, n, B, m,
+    n_max, sel_ld, out) with ``logits`` contiguous and the integers as ``int``."""
     _require(torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32,
              "logits must be fp32 on a ROCm device")
     _require(logits.dim() == 2 and logits.shape[1] == 2, "logits must be [n, 2]")
@@ -128,7 +122,30 @@ def select(logits, labels, doc_off, m, n_max, totals, grams=None, sel_ld=None, o
     _require(totals.shape == (4,), "totals must be [4]")
     B, m, n_max = doc_off.numel() - 1, int(m), int(n_max)
     _require(m >= 0, "m must be >= 0")
-    gram_max = 0
+    need = n_max if m == 0 else min(m, n_max)
+    sel_ld = need if sel_ld is None else int(sel_ld)
+    _require(sel_ld >= need, f"sel_ld {sel_ld} below {need}")
+    if out is None:
+        out = (torch.empty(B, sel_ld, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, 4, dtype=torch.int32, device=dev))
+    for name, t, shape in zip(("sel", "nsel", "doc_counts"), out, ((B, sel_ld), (B,), (B, 4))):
+        _require(t.device == dev and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape,
+                 f"{name} must be contiguous int32 {shape} on the logits' device")
+    return logits.contiguous(), n, B, m, n_max, sel_ld, out
+
+
+def supported(n_max, gram_max=0):
+    return bool(load().hsg_eval_select_supported(int(n_max), int(gram_max)))
+
+
+def select(logits, labels, doc_off, m, n_max, totals, grams=None, sel_ld=None, out=None):
+    """``hsg_eval_select`` on device tensors: returns (sel int32 [B, sel_ld], nsel int32 [B],
+    doc_counts int32 [B, 4]) and adds the batch's counters into ``totals`` (int64 [4], on the
+    device, accumulated).  ``grams``: a device :class:`GramPack` for n-gram blocking, or
+    None.  ``out``: optional (sel, nsel, doc_counts) to write into.  Nothing here waits for
+    the device."""
+    logits, n, B, m, n_max, sel_ld, (sel, nsel, doc_counts) = _batch(logits, labels, doc_off, m, n_max, totals, sel_ld, out)
+    dev, gram_max = logits.device, 0
     gp = gi = gc = None
     if grams is not None:
         _require(grams.buf.device == dev and grams.buf.dtype == torch.int32 and grams.buf.is_contiguous(),
@@ -138,17 +155,6 @@ def select(logits, labels, doc_off, m, n_max, totals, grams=None, sel_ld=None, o
         gram_max = int(grams.gram_max)
     _require(supported(n_max, gram_max),
              f"n_max {n_max} / gram_max {gram_max} beyond hsg_eval_select_supported (1..1024 rows, 0..262144 n-grams)")
-    need = n_max if m == 0 else min(m, n_max)
-    sel_ld = need if sel_ld is None else int(sel_ld)
-    _require(sel_ld >= need, f"sel_ld {sel_ld} below {need}")
-    if out is None:
-        out = (torch.empty(B, sel_ld, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-               torch.empty(B, 4, dtype=torch.int32, device=dev))
-    sel, nsel, doc_counts = out
-    for name, t, shape in (("sel", sel, (B, sel_ld)), ("nsel", nsel, (B,)), ("doc_counts", doc_counts, (B, 4))):
-        _require(t.device == dev and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape,
-                 f"{name} must be contiguous int32 {shape} on the logits' device")
-    logits = logits.contiguous()
     check(load().hsg_eval_select(n, B, ptr(logits), ptr(labels), ptr(doc_off), m, n_max, ptr(gp), ptr(gi), ptr(gc),
                                  gram_max, ptr(sel), sel_ld, ptr(nsel), ptr(doc_counts), ptr(totals),
                                  stream_of(logits)), "hsg_eval_select")
@@ -252,19 +258,8 @@ def select_words(logits, labels, doc_off, m, n_max, n_win, totals, words=None, t
     windows of ``n_win`` words, or None.  ``tab_cap`` defaults to the pack's own rule.
     ``out``: optional (sel, nsel, doc_counts) to write into.  Nothing here waits for the
     device."""
-    _require(torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32,
-             "logits must be fp32 on a ROCm device")
-    _require(logits.dim() == 2 and logits.shape[1] == 2, "logits must be [n, 2]")
-    dev, n = logits.device, logits.shape[0]
-    for name, t, dt in (("labels", labels, torch.int64), ("doc_off", doc_off, torch.int32),
-                        ("totals", totals, torch.int64)):
-        _require(torch.is_tensor(t) and t.device == dev and t.dtype == dt and t.is_contiguous(),
-                 f"{name} must be contiguous {dt} on the logits' device")
-    _require(labels.shape == (n,), "labels must be [n]")
-    _require(doc_off.dim() == 1 and doc_off.numel() >= 2, "doc_off must be [B + 1] with B >= 1")
-    _require(totals.shape == (4,), "totals must be [4]")
-    B, m, n_max, n_win = doc_off.numel() - 1, int(m), int(n_max), int(n_win)
-    _require(m >= 0, "m must be >= 0")
+    logits, n, B, m, n_max, sel_ld, (sel, nsel, doc_counts) = _batch(logits, labels, doc_off, m, n_max, totals, sel_ld, out)
+    dev, n_win = logits.device, int(n_win)
     wp = wi = None
     if words is not None:
         _require(words.buf.device == dev and words.buf.dtype == torch.int32 and words.buf.is_contiguous(),
@@ -277,17 +272,6 @@ def select_words(logits, labels, doc_off, m, n_max, n_win, totals, words=None, t
     _require(words_supported(n_max, n_win, tab_cap),
              f"n_max {n_max} / n_win {n_win} / tab_cap {tab_cap} beyond hsg_eval_words_supported (1..1024 rows, windows "
              "of 1..8 words, a power of two of 64..8192 slots)")
-    need = n_max if m == 0 else min(m, n_max)
-    sel_ld = need if sel_ld is None else int(sel_ld)
-    _require(sel_ld >= need, f"sel_ld {sel_ld} below {need}")
-    if out is None:
-        out = (torch.empty(B, sel_ld, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-               torch.empty(B, 4, dtype=torch.int32, device=dev))
-    sel, nsel, doc_counts = out
-    for name, t, shape in (("sel", sel, (B, sel_ld)), ("nsel", nsel, (B,)), ("doc_counts", doc_counts, (B, 4))):
-        _require(t.device == dev and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape,
-                 f"{name} must be contiguous int32 {shape} on the logits' device")
-    logits = logits.contiguous()
     check(load().hsg_eval_select_words(n, B, ptr(logits), ptr(labels), ptr(doc_off), m, n_max, n_win, ptr(wp), ptr(wi),
                                        tab_cap, ptr(sel), sel_ld, ptr(nsel), ptr(doc_counts), ptr(totals),
                                        stream_of(logits)), "hsg_eval_select_words")
