@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.utils.rnn as rnn
 
 from hetersumgraph_amd import lstm as hl
+from model_ref import run_packed as _run_packed, single_layers as _single_layers
 from oracle import masks
 
 pytestmark = pytest.mark.gpu
@@ -38,34 +39,6 @@ def make_rows(seed, lens, width):
     g = torch.Generator().manual_seed(seed)
     n = sum(lens)
     return torch.randn(n, 300, generator=g), torch.randn(n, width, generator=g)
-
-
-def _run_packed(mod, x, lens):
-    """mod over rows x laid end to end (documents of lens > 0) -> rows [n, ndir*hid]."""
-    lens = [g for g in lens if g > 0]                     # packing takes no empty sequence
-    n_doc, max_len = len(lens), max(lens)
-    doc = torch.repeat_interleave(torch.arange(n_doc), torch.tensor(lens))
-    pos = torch.cat([torch.arange(g) for g in lens])
-    flat = doc * max_len + pos
-    pad = x.new_zeros(n_doc * max_len, x.shape[1]).index_copy(0, flat, x).view(n_doc, max_len, -1)
-    out, _ = mod(rnn.pack_padded_sequence(pad, lens, batch_first=True, enforce_sorted=False))
-    unp, _ = rnn.pad_packed_sequence(out, batch_first=True, total_length=max_len)
-    return unp.reshape(n_doc * max_len, -1).index_select(0, flat)
-
-
-def _single_layers(lstm, dtype):
-    """The module restated as single-layer LSTMs holding the same weights."""
-    ndir = 2 if lstm.bidirectional else 1
-    mods = []
-    for layer in range(lstm.num_layers):
-        m = nn.LSTM(lstm.input_size if layer == 0 else ndir * lstm.hidden_size, lstm.hidden_size, num_layers=1,
-                    batch_first=True, bidirectional=lstm.bidirectional).to(dtype)
-        with torch.no_grad():
-            for names in hl._names(layer, ndir):
-                for nm in names:
-                    getattr(m, nm.replace(f"_l{layer}", "_l0")).copy_(getattr(lstm, nm).to(dtype))
-        mods.append(m)
-    return mods
 
 
 def _cell_states(mod, x, lens):
