@@ -67,6 +67,10 @@ EVALW_EXPORTS = ("hsg_eval_words_supported", "hsg_eval_select_words")
 EVALT_EXPORTS = ("hsg_eval_text_supported", "hsg_eval_text_word_bound", "hsg_eval_text_workspace_bytes",
                  "hsg_eval_text_words")
 
+# every symbol include/hsg_resident.h declares (checked by tests/test_resident_abi.py); bound
+# from RES_SIGS, as EVAL_SIGS
+RES_EXPORTS = ("hsg_res_supported", "hsg_res_offsets", "hsg_res_graph", "hsg_res_relation")
+
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
 HSG_EPI_ADD = 2
@@ -93,6 +97,30 @@ class HsgMtTensor(ctypes.Structure):
     _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
                 ("n", ctypes.c_int64)]
 
+
+class HsgResRel(ctypes.Structure):
+    """Mirror of ``struct hsg_res_rel`` (include/hsg_resident.h)."""
+
+    _fields_ = [(k, ctypes.c_void_p) for k in ("indptr", "src", "tf", "eid", "phantom", "cindptr", "cdst", "cperm",
+                                               "src_nodes", "dst_nodes")]
+
+
+class HsgResStore(ctypes.Structure):
+    """Mirror of ``struct hsg_res_store`` (include/hsg_resident.h)."""
+
+    _fields_ = [("n_docs", ctypes.c_int64), ("starts", ctypes.c_void_p), ("bases", ctypes.c_void_p),
+                ("sent_len", ctypes.c_int32), ("label_len", ctypes.c_int32),
+                ("unit", ctypes.c_void_p), ("ndtype", ctypes.c_void_p), ("id", ctypes.c_void_p),
+                ("sent_rank", ctypes.c_void_p), ("words", ctypes.c_void_p), ("label", ctypes.c_void_p),
+                ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("tffrac", ctypes.c_void_p),
+                ("edtype", ctypes.c_void_p), ("rel", HsgResRel * 2)]
+
+
+# count families of the resident store (include/hsg_resident.h); q = 0 (W2S), 1 (S2W)
+HSG_RES_NODE, HSG_RES_EDGE, HSG_RES_SENT, HSG_RES_NFAM = 0, 1, 2, 9
+HSG_RES_SRC = lambda q: 3 + 3 * q
+HSG_RES_DST = lambda q: 4 + 3 * q
+HSG_RES_TYP = lambda q: 5 + 3 * q
 
 _lib = None
 
@@ -251,6 +279,13 @@ EVALT_SIGS = {
     "hsg_eval_text_workspace_bytes": [_I, _I, _L64],
     "hsg_eval_text_words": [_I, _I, _P, _L64, _P, _P, _L64, _P, _P, _P, _P],
 }
+_RESP = ctypes.POINTER(HsgResStore)
+RES_SIGS = {
+    "hsg_res_supported": [_I, _L64, _L64, _L64],
+    "hsg_res_offsets": [_RESP, _I, _P, _P, _P],
+    "hsg_res_graph": [_RESP, _I, _P, _P, _L64, _L64] + [_P] * 11,
+    "hsg_res_relation": [_RESP, _I, _I, _P, _P, _L64, _L64, _L64] + [_P] * 11,
+}
 EVALT_RESTYPE = {"hsg_eval_text_word_bound": ctypes.c_int64, "hsg_eval_text_workspace_bytes": ctypes.c_size_t}
 
 
@@ -272,7 +307,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = EMBED_RESTYPE.get(name, ctypes.c_int)
-    for sigs in (EVAL_SIGS, EVALW_SIGS):
+    for sigs in (EVAL_SIGS, EVALW_SIGS, RES_SIGS):
         for name, args in sigs.items():
             fn = getattr(lib, name)
             fn.argtypes = args

@@ -1,0 +1,433 @@
+"""Device-resident document store with on-device batch assembly (opt-in by import).
+
+A document's graph columns, its sentence rows and its two hot relations (W2S, S2W) are pure
+functions of the example.  :class:`DocumentStore` builds them once, keeps them on the device
+in narrow types, and :meth:`DocumentStore.batch` assembles a batch with four launches
+(include/hsg_resident.h: the running offsets, the graph columns, one per relation) instead of
+``graph_collate_fn`` + ``DGLGraph.to``: no per-column copy, no segmented sort, and -- unless
+the batch needs a work list (``relation.attach_work_lists``) -- no device-to-host copy and no
+synchronise.
+
+Why the relations of a batch are the concatenation of its documents': ``hsg_rel_build``'s
+CSR is the typed edge list in edge-id order stably sorted by destination rank, its CSC that
+CSR stably sorted by source rank, and documents are contiguous in node and edge order -- so
+inside a batch every document's slice holds the document's own relation plus five running
+offsets (node, edge, source rank, destination rank, typed edge).  tests/resident_ref.py
+restates the assembly in numpy and pins it against ``graph.batch`` and the relation oracle.
+
+There is no fallback: a CPU device, a pick outside the store or a batch beyond
+``hsg_res_supported`` raises.  Changing a dataset after its store was built is the caller's
+business (the store does not look at the dataset again).
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .graph import BatchedDGLGraph, Frame
+from .relation import HOT_KINDS, KINDS, Relation, attach_work_lists, build_relation
+from .relation import PIECE_MIN, PIECE_MULT
+
+NODE, EDGE, SENT, NFAM = _lib.HSG_RES_NODE, _lib.HSG_RES_EDGE, _lib.HSG_RES_SENT, _lib.HSG_RES_NFAM
+SRC, DST, TYP = _lib.HSG_RES_SRC, _lib.HSG_RES_DST, _lib.HSG_RES_TYP
+I32_MAX = 2 ** 31 - 1
+REL_ARRAYS = ("indptr", "src", "tf", "eid", "phantom", "cindptr", "cdst", "cperm", "src_nodes", "dst_nodes")
+
+
+def _narrow(a, dtype, what, doc):
+    """``a`` as ``dtype`` when every value survives the round trip; raises otherwise."""
+    a = np.asarray(a)
+    b = a.astype(dtype)
+    if not np.array_equal(b.astype(a.dtype), a):
+        raise ValueError(f"document {doc}: '{what}' holds a value that does not fit {np.dtype(dtype).name}")
+    return b
+
+
+def needs_work_list(n, n_typed, longest, piece_min=None, piece_mult=None):
+    """``hsg_rel_work``'s rule on the host: does a CSR / CSC of ``n`` segments over ``n_typed``
+    edges, the longest of ``longest`` edges, get a work list?  A segment is split when it is
+    longer than ``P = max(PIECE_MIN, PIECE_MULT * ceil(n_typed / n))``."""
+    pmin = int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN))) if piece_min is None else piece_min
+    mult = int(_lib.path_option("HSG_PIECE_MULT", str(PIECE_MULT))) if piece_mult is None else piece_mult
+    if n <= 0 or pmin <= 0:
+        return False
+    return longest > max(pmin, mult * (-(-n_typed // n)))
+
+
+def batch_order(n_sent):
+    """``graph_collate_fn``'s rule made total: descending sentence count, ties in the order
+    given (positions into ``n_sent``)."""
+    return np.argsort(-np.asarray(n_sent, np.int64), kind="stable")
+
+
+def doc_counts(doc):
+    """Host counts of one ``synth.DocArrays``: ``[NFAM]`` family counts and, per kind, the
+    longest CSR (by destination) and CSC (by source) segment of its typed edges."""
+    unit, src, dst = np.asarray(doc.unit), np.asarray(doc.src), np.asarray(doc.dst)
+    cnt = np.zeros(NFAM, np.int64)
+    cnt[NODE], cnt[EDGE], cnt[SENT] = doc.n_nodes, len(src), len(doc.sent_nodes)
+    longest = np.zeros((2, 2), np.int64)
+    for q, kind in enumerate(HOT_KINDS):
+        su, du = KINDS[kind]
+        typed = (unit[src] == su) & (unit[dst] == du) if len(src) else np.zeros(0, bool)
+        cnt[SRC(q)], cnt[DST(q)], cnt[TYP(q)] = (unit == su).sum(), (unit == du).sum(), typed.sum()
+        if typed.any():
+            longest[q, 0] = np.bincount(dst[typed]).max()
+            longest[q, 1] = np.bincount(src[typed]).max()
+    return cnt, longest
+
+
+class ResidentBatch(BatchedDGLGraph):
+    """A batch assembled by :meth:`DocumentStore.batch`: a ``BatchedDGLGraph`` on the store's
+    device whose frames and relations are already there.  The host-side structural views
+    (``host_column``, ``_src`` / ``_dst``) come from the store's host copies of the picked
+    documents: the node views eagerly, the edge views on first use."""
+
+    def __init__(self):
+        self._h_src = self._h_dst = None
+        self._origin = None               # (store, slots) until a structural column is written
+        super().__init__()
+
+    def _edges(self):
+        if self._h_src is None and self._origin is not None:
+            store, slots = self._origin
+            self._h_src, self._h_dst = store._host_edge_lists(slots)
+
+    @property
+    def _src(self):
+        self._edges()
+        return self._h_src
+
+    @_src.setter
+    def _src(self, v):
+        self._h_src = v
+
+    @property
+    def _dst(self):
+        self._edges()
+        return self._h_dst
+
+    @_dst.setter
+    def _dst(self, v):
+        self._h_dst = v
+
+    def number_of_edges(self):
+        if self._origin is not None and not self._pending:
+            return int(sum(self.batch_num_edges))
+        return super().number_of_edges()
+
+    num_edges = number_of_edges
+
+    def _src_t(self):
+        if self._dev_src is None:
+            return super()._src_t()
+        return self._dev_src
+
+    def host_column(self, key):
+        if self._origin is not None and key in ("tffrac", "edtype") and key not in self._host_cols:
+            store, slots = self._origin
+            self._host_cols.update(store._host_edge_columns(slots))
+        return super().host_column(key)
+
+    def _detach(self):
+        """A structural write: the store's host copies no longer describe this graph."""
+        if self._origin is not None:
+            self._edges()
+            self._origin = None
+
+    def _mutated(self):
+        self._detach()
+        super()._mutated()
+
+    def _touch_column(self, key, is_node):
+        if key in ("unit", "dtype", "tffrac"):
+            self._detach()
+        super()._touch_column(key, is_node)
+
+    def to(self, device, **kwargs):
+        device = _device(device, allow_cpu=True)
+        if device == self.device:
+            return self
+        self._detach()
+        return super().to(device, **kwargs)
+
+    def __getstate__(self):
+        self._detach()
+        return super().__getstate__()
+
+
+def _device(device, allow_cpu=False):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device.type != "cuda" and not allow_cpu:
+        raise RuntimeError("the resident document store lives on a ROCm device (hsg_res_*); no CPU fallback")
+    return device
+
+
+class DocumentStore:
+    """Every document of a dataset, on the device (see the module docstring)."""
+
+    # ------------------------------------------------------------------ build
+    def __init__(self, device):
+        self.device = _device(device)
+        self._docs = 0
+
+    @classmethod
+    def from_doc_arrays(cls, docs, device, chunk=256, indices=None, eval_words=None):
+        """``docs``: a list of ``synth.DocArrays``; ``indices``: the dataset index of each
+        (default: its position); ``eval_words``: per document, what ``G.eval_words`` of its
+        one-member batch holds (``ExampleSet(eval_words=True)``)."""
+        docs = list(docs)
+        return cls._build([docs[i:i + chunk] for i in range(0, len(docs), max(1, int(chunk)))], device, indices,
+                          eval_words)
+
+    @classmethod
+    def from_dataset(cls, dataset, device, indices=None, chunk=256):
+        """``dataset``: an ``ExampleSet`` / ``MultiExampleSet``; the documents come from
+        ``dataset.graph_arrays`` in chunks of ``chunk``."""
+        indices = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
+        words = [] if getattr(dataset, "eval_words", False) else None
+
+        def chunks():
+            for i in range(0, len(indices), max(1, int(chunk))):
+                idx = indices[i:i + chunk]
+                if words is None:
+                    yield dataset.graph_arrays(idx)
+                    continue
+                from .evalsel import word_ids
+                items = [dataset.get_example(j) for j in idx]
+                for it in items:
+                    rows = min(len(it.original_article_sents), dataset.doc_max_timesteps)
+                    words.append([word_ids(it.original_article_sents, rows)])
+                yield dataset.graph_arrays(idx, items)
+        return cls._build(chunks(), device, indices, words)
+
+    @classmethod
+    def _build(cls, chunks, device, indices, eval_words):
+        self = cls(device)
+        dev = self.device
+        counts, longest, bases = [], [], []
+        host = {k: [] for k in ("unit", "ndtype", "src", "dst", "tffrac", "edtype")}
+        cols = {k: [] for k in ("unit", "ndtype", "id", "sent_rank", "words", "label", "src", "dst", "tffrac", "edtype")}
+        rels = [{k: [] for k in REL_ARRAYS} for _ in HOT_KINDS]
+        self.sent_len = self.label_len = None
+        n_seen = 0
+        for docs in chunks:
+            if not docs:
+                continue
+            base = np.zeros(NFAM, np.int64)
+            part = {k: [] for k in cols}
+            for doc in docs:
+                no = n_seen
+                n_seen += 1
+                cnt, lng = doc_counts(doc)
+                n, N = int(cnt[NODE]), int(cnt[SENT])
+                words, label = np.asarray(doc.words), np.asarray(doc.label)
+                if words.ndim != 2 or label.ndim != 2 or len(words) != N or len(label) != N:
+                    raise ValueError(f"document {no}: 'words' / 'label' are not [sentences, width]")
+                if self.sent_len is None:
+                    self.sent_len, self.label_len = int(words.shape[1]), int(label.shape[1])
+                if (words.shape[1], label.shape[1]) != (self.sent_len, self.label_len):
+                    raise ValueError(f"document {no}: sentence rows of another width than the store's")
+                if not np.array_equal(np.asarray(doc.position).reshape(-1), np.arange(1, N + 1)):
+                    raise ValueError(f"document {no}: 'position' is not 1..N (the store does not keep it)")
+                sn = np.asarray(doc.sent_nodes, np.int64)
+                if len(np.unique(sn)) != N or (N and (sn.min() < 0 or sn.max() >= n)):
+                    raise ValueError(f"document {no}: sentence nodes repeat or lie outside the document")
+                if cnt[EDGE] and (min(doc.src.min(), doc.dst.min()) < 0 or max(doc.src.max(), doc.dst.max()) >= n):
+                    raise ValueError(f"document {no}: an edge references a node outside the document")
+                if base[NODE] + n > I32_MAX or base[EDGE] + cnt[EDGE] > I32_MAX:
+                    raise ValueError("a build chunk beyond 2^31 - 1 nodes or edges: use a smaller chunk")
+                rank = np.full(n, -1, np.int32)
+                rank[sn] = np.arange(N, dtype=np.int32)
+                u8 = {k: _narrow(getattr(doc, k), np.uint8, k, no) for k in ("unit", "ndtype", "tffrac", "edtype")}
+                src, dst = _narrow(doc.src, np.int32, "src", no), _narrow(doc.dst, np.int32, "dst", no)
+                for k in ("unit", "ndtype", "tffrac", "edtype"):
+                    host[k].append(u8[k])
+                    part[k].append(u8[k])
+                host["src"].append(src)
+                host["dst"].append(dst)
+                part["src"].append(src + np.int32(base[NODE]))
+                part["dst"].append(dst + np.int32(base[NODE]))
+                part["id"].append(_narrow(doc.wid, np.int32, "id", no))
+                part["sent_rank"].append(rank)
+                part["words"].append(_narrow(words, np.int32, "words", no).reshape(-1))
+                part["label"].append(_narrow(label, np.uint8, "label", no).reshape(-1))
+                counts.append(cnt)
+                longest.append(lng)
+                bases.append(base.copy())
+                base += cnt
+            cat = {k: torch.from_numpy(np.concatenate(v)).to(dev) for k, v in part.items()}
+            for k, v in cat.items():
+                cols[k].append(v)
+            # the chunk's relations, by today's builder; chunk-relative values are kept as they are
+            for q, kind in enumerate(HOT_KINDS):
+                rel = build_relation(kind, cat["src"], cat["dst"], cat["unit"], cat["tffrac"], cat["edtype"])
+                if (rel.n_src, rel.n_dst, rel.n_typed) != (base[SRC(q)], base[DST(q)], base[TYP(q)]):
+                    raise RuntimeError(f"{kind}: hsg_rel_build disagrees with the host counts of the chunk")
+                d = rel.dev
+                for k in REL_ARRAYS:
+                    a = d[k][:rel.n_dst] if k == "indptr" else d[k][:rel.n_src] if k == "cindptr" else d[k]
+                    rels[q][k].append(a.to(torch.uint8 if k == "tf" else torch.int32))
+        if not counts:
+            raise ValueError("an empty document store")
+        self._docs = len(counts)
+        self.counts = np.stack(counts)                                    # [n_docs, NFAM]
+        self.longest = np.stack(longest)                                  # [n_docs, kind, CSR / CSC]
+        self.starts = np.zeros((NFAM, self._docs + 1), np.int64)
+        self.starts[:, 1:] = np.cumsum(self.counts, 0).T
+        self.bases = np.ascontiguousarray(np.stack(bases).T)              # [NFAM, n_docs]
+        self.indices = list(range(self._docs)) if indices is None else [int(i) for i in indices]
+        if len(self.indices) != self._docs or len(set(self.indices)) != self._docs:
+            raise ValueError("indices: one distinct dataset index per document")
+        self._slot_of = {ix: s for s, ix in enumerate(self.indices)}
+        self.eval_words = None if eval_words is None else list(eval_words)
+        self._host = {k: np.concatenate(v) for k, v in host.items()}
+        self._cols = {k: torch.cat(v) for k, v in cols.items()}
+        self._rels = [{k: torch.cat(v) for k, v in r.items()} for r in rels]
+        self._starts_d = torch.from_numpy(self.starts).to(dev)
+        self._bases_d = torch.from_numpy(self.bases).to(dev)
+        p = _lib.ptr
+        self._cstruct = _lib.HsgResStore(
+            self._docs, p(self._starts_d), p(self._bases_d), self.sent_len, self.label_len,
+            *[p(self._cols[k]) for k in ("unit", "ndtype", "id", "sent_rank", "words", "label", "src", "dst",
+                                         "tffrac", "edtype")],
+            (_lib.HsgResRel * 2)(*[_lib.HsgResRel(*[p(r[k]) for k in REL_ARRAYS]) for r in self._rels]))
+        torch.cuda.synchronize(dev)        # the build's host arrays may go once the uploads are done
+        return self
+
+    def __len__(self):
+        return self._docs
+
+    def _tensors(self):
+        return list(self._cols.values()) + [t for r in self._rels for t in r.values()] + [self._starts_d, self._bases_d]
+
+    @property
+    def nbytes(self):
+        """Bytes of device memory the store holds."""
+        return int(sum(t.numel() * t.element_size() for t in self._tensors()))
+
+    # ------------------------------------------------------------ host views
+    def _host_slices(self, key, fam, slots):
+        a, st = self._host[key], self.starts[fam]
+        return [a[st[s]:st[s + 1]] for s in slots]
+
+    def _host_node_columns(self, slots):
+        f = lambda k: np.concatenate(self._host_slices(k, NODE, slots)).astype(np.float32)
+        return {"unit": f("unit"), "ndtype": f("ndtype")}
+
+    def _host_edge_columns(self, slots):
+        cat = lambda k: np.concatenate(self._host_slices(k, EDGE, slots))
+        return {"tffrac": cat("tffrac").astype(np.int64), "edtype": cat("edtype").astype(np.float32)}
+
+    def _host_edge_lists(self, slots):
+        noff = np.concatenate([[0], np.cumsum(self.counts[slots, NODE])])
+        out = []
+        for k in ("src", "dst"):
+            out.append(np.concatenate([a.astype(np.int64) + o
+                                       for a, o in zip(self._host_slices(k, EDGE, slots), noff)] or
+                                      [np.zeros(0, np.int64)]))
+        return tuple(out)
+
+    # ----------------------------------------------------------------- batch
+    def slots_of(self, indices):
+        try:
+            return np.asarray([self._slot_of[int(i)] for i in indices], np.int64)
+        except KeyError as e:
+            raise IndexError(f"document {e.args[0]} is not in the store") from None
+
+    def batch(self, indices):
+        """``(G, index)`` as ``graph_collate_fn`` gives them for the same documents: sorted by
+        sentence count (descending, ties in the order given), ``G`` on the device."""
+        slots = self.slots_of(indices)
+        B = len(slots)
+        if B < 1:
+            raise ValueError("an empty batch")
+        slots = slots[batch_order(self.counts[slots, SENT])]
+        tot = self.counts[slots].sum(0)
+        lib, dev = _lib.load(), self.device
+        n, E = int(tot[NODE]), int(tot[EDGE])
+        if not lib.hsg_res_supported(B, n, E, int(max(tot[TYP(0)], tot[TYP(1)]))):
+            raise RuntimeError(f"batch of {B} documents, {n} nodes, {E} edges: beyond hsg_res_supported")
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        i32, i64, f32 = torch.int32, torch.int64, torch.float32
+        L, M = self.sent_len, self.label_len
+        with torch.cuda.device(dev):
+            # one small pinned copy, not waited for (the pinned block is recycled stream-safely)
+            pick = torch.from_numpy(slots.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+            offs = new(NFAM * (B + 1), i64)
+            st = _lib.stream_of(offs)
+            cs = ctypes.byref(self._cstruct)
+            p = _lib.ptr
+            _lib.check(lib.hsg_res_offsets(cs, B, p(pick), p(offs), st), "hsg_res_offsets")
+            nd = dict(unit=new(n, f32), dtype=new(n, f32), id=new(n, i64), words=new((n, L), i64),
+                      position=new((n, 1), i64), label=new((n, M), i64))
+            src, dst = new(E, i64), new(E, i64)
+            ed = dict(tffrac=new(E, i64), dtype=new(E, f32))
+            _lib.check(lib.hsg_res_graph(cs, B, p(pick), p(offs), n, E, p(nd["unit"]), p(nd["dtype"]), p(nd["id"]),
+                                         p(nd["words"]), p(nd["position"]), p(nd["label"]), p(src), p(dst),
+                                         p(ed["tffrac"]), p(ed["dtype"]), st), "hsg_res_graph")
+            G = ResidentBatch()
+            G._n, G.device = n, dev
+            G._nframe, G._ef = Frame(n, dev), Frame(E, dev)
+            G._nframe.cols, G._ef.cols = nd, ed
+            G._dev_src, G._dev_dst = src, dst
+            G.batch_size = B
+            G.batch_num_nodes = [int(x) for x in self.counts[slots, NODE]]
+            G.batch_num_edges = [int(x) for x in self.counts[slots, EDGE]]
+            G._origin = (self, slots)
+            G._h_src = G._h_dst = None                 # formed from the store on first use
+            G._host_cols.update(self._host_node_columns(slots))
+            G.resident_work_lists = {}
+            for q, kind in enumerate(HOT_KINDS):
+                ns, ndst, nt = int(tot[SRC(q)]), int(tot[DST(q)]), int(tot[TYP(q)])
+                d = dict(indptr=new(ndst + 1, i32), src=new(nt, i32), tf=new(nt, torch.uint8), eid=new(nt, i64),
+                         phantom=new(ndst, i32), cindptr=new(ns + 1, i32), cdst=new(nt, i32), cperm=new(nt, i32),
+                         src_nodes=new(ns, i64), dst_nodes=new(ndst, i64))
+                _lib.check(lib.hsg_res_relation(cs, q, B, p(pick), p(offs), ns, ndst, nt,
+                                                *[p(d[k]) for k in REL_ARRAYS], st), "hsg_res_relation")
+                lng = self.longest[slots, q].max(0)
+                need = needs_work_list(ndst, nt, int(lng[0])) or needs_work_list(ns, nt, int(lng[1]))
+                G.resident_work_lists[kind] = need
+                if need:
+                    attach_work_lists(d, ns, ndst, nt)         # today's path, with its read-back
+                G._rel_cache[("rel", kind, str(dev))] = Relation.on_device(kind, ns, ndst, d, E)
+            # the launches above read pick and offs after this returns: the allocator keeps a
+            # freed block for later work of the SAME stream, so dropping them here is safe
+        if self.eval_words is not None:
+            G.eval_words = [w for s in slots for w in self.eval_words[s]]
+        return G, [self.indices[s] for s in slots]
+
+
+class ResidentLoader:
+    """Iterates ``(G, index)`` like ``DataLoader(dataset, batch_size, shuffle, collate_fn=
+    graph_collate_fn)``, from a :class:`DocumentStore`.  The permutation is drawn on the host
+    from ``generator``; ``index`` holds dataset indices."""
+
+    def __init__(self, store, batch_size, shuffle=False, generator=None, drop_last=False):
+        if batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
+        self.store, self.batch_size, self.shuffle = store, int(batch_size), shuffle
+        self.generator, self.drop_last = generator, drop_last
+
+    def __len__(self):
+        n = len(self.store)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def batches(self):
+        """The dataset indices of every batch of one epoch, before the sort by length."""
+        n = len(self.store)
+        order = torch.randperm(n, generator=self.generator).tolist() if self.shuffle else range(n)
+        picks = [self.store.indices[s] for s in order]
+        out = [picks[i:i + self.batch_size] for i in range(0, n, self.batch_size)]
+        if self.drop_last and out and len(out[-1]) < self.batch_size:
+            out.pop()
+        return out
+
+    def __iter__(self):
+        for idx in self.batches():
+            yield self.store.batch(idx)
