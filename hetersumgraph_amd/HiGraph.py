@@ -183,6 +183,8 @@ class HSumGraph(nn.Module):
         n_pos = self.ngram_enc.position_embedding.weight.shape[0]
         if ids.dim() != 2 or ids.shape[0] == 0 or not 7 <= ids.shape[1] <= n_pos - 1:
             return None                      # today's path states what is wrong with the batch
+        if self.ngram_enc.takes_token_path(ids):
+            return None                      # HSG_SENT_CNN, frozen table: the encoder reads the ids itself
         return ids
 
     def _embed_both(self, graph, wid, ids):

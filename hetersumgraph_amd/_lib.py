@@ -71,6 +71,11 @@ EVALT_EXPORTS = ("hsg_eval_text_supported", "hsg_eval_text_word_bound", "hsg_eva
 # from RES_SIGS, as EVAL_SIGS
 RES_EXPORTS = ("hsg_res_supported", "hsg_res_offsets", "hsg_res_graph", "hsg_res_relation")
 
+# every symbol include/hsg_cnn_tokens.h declares (checked by tests/test_cnn_tokens_abi.py);
+# bound from CNNTOK_SIGS / CNNTOK_RESTYPE, as EMBED_SIGS
+CNNTOK_EXPORTS = ("hsg_cnn_tok_supported", "hsg_cnn_tok_mark", "hsg_cnn_tok_table", "hsg_cnn_tok_pool",
+                  "hsg_cnn_tok_chunk", "hsg_cnn_tok_dw_ws_floats", "hsg_cnn_tok_dw")
+
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
 HSG_EPI_ADD = 2
@@ -286,6 +291,16 @@ RES_SIGS = {
     "hsg_res_graph": [_RESP, _I, _P, _P, _L64, _L64] + [_P] * 11,
     "hsg_res_relation": [_RESP, _I, _I, _P, _P, _L64, _L64, _L64] + [_P] * 11,
 }
+CNNTOK_SIGS = {
+    "hsg_cnn_tok_supported": [_I, _I],
+    "hsg_cnn_tok_mark": [_I, _I, _I, _P, _P, _P, _P],
+    "hsg_cnn_tok_table": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "hsg_cnn_tok_pool": [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P],
+    "hsg_cnn_tok_chunk": [],
+    "hsg_cnn_tok_dw_ws_floats": [_I, _I],
+    "hsg_cnn_tok_dw": [_I, _I, _I, _I] + [_P] * 8 + [_P, _I, _P, _P],
+}
+CNNTOK_RESTYPE = {"hsg_cnn_tok_dw_ws_floats": ctypes.c_size_t}
 EVALT_RESTYPE = {"hsg_eval_text_word_bound": ctypes.c_int64, "hsg_eval_text_workspace_bytes": ctypes.c_size_t}
 
 
@@ -316,6 +331,10 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = EVALT_RESTYPE.get(name, ctypes.c_int)
+    for name, args in CNNTOK_SIGS.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = CNNTOK_RESTYPE.get(name, ctypes.c_int)
     _lib = lib
     return lib
 

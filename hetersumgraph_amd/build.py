@@ -19,13 +19,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SOURCES = [os.path.join(HERE, "csrc", f) for f in ("hsg_gat.hip", "hsg_attn.hip", "hsg_gemm.hip", "hsg_rows.hip", "hsg_hproj.hip", "hsg_relbuild.hip", "hsg_cnn.hip", "hsg_ffn.hip", "hsg_dw.hip",
                                                      "hsg_lstm.hip", "hsg_train.hip", "hsg_model.hip", "hsg_embed.hip", "hsg_eval.hip",
-                                                     "hsg_eval_text.hip", "hsg_resident.hip")]
+                                                     "hsg_eval_text.hip", "hsg_resident.hip", "hsg_cnn_tokens.hip")]
 OUT = os.path.join(HERE, "libhsg.so")
 OBJDIR = os.path.join(ROOT, "build", "obj")
 DEV_OUT = os.path.join(HERE, "libhsg_dev.so")
 DEV_OBJDIR = os.path.join(ROOT, "build", "obj_dev")
 ARCH = os.environ.get("HSG_OFFLOAD_ARCH", "gfx950")
-HEADERS = [os.path.join(ROOT, "include", h) for h in ("hsg.h", "hsg_train.h", "hsg_model.h", "hsg_embed.h", "hsg_eval.h", "hsg_eval_words.h", "hsg_eval_text.h", "hsg_resident.h")] + [os.path.join(HERE, "csrc", h) for h in
+HEADERS = [os.path.join(ROOT, "include", h) for h in ("hsg.h", "hsg_train.h", "hsg_model.h", "hsg_embed.h", "hsg_eval.h", "hsg_eval_words.h", "hsg_eval_text.h", "hsg_resident.h", "hsg_cnn_tokens.h")] + [os.path.join(HERE, "csrc", h) for h in
                                                       ("hsg_rng.h", "hsg_wsplit.h", "hsg_dev.h", "hsg_wave.h")]
 # host-only graph builder (no HIP runtime: usable in DataLoader workers)
 HOST_SOURCES = [os.path.join(HERE, "csrc", "hsg_graphbuild.cpp")]
@@ -55,7 +55,10 @@ def _flags(dev=False):
 
 # per-file extra flags: the narrow-head projection wants plain v_fmac_f32 (SGPR weight
 # operand) rather than SLP-packed v_pk_fma_f32, which issues slower on gfx950
-FILE_FLAGS = {"hsg_hproj.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {"hsg_hproj.hip": ["-fno-slp-vectorize"],
+              # the token paths' order contracts are written in separately rounded multiplies and
+              # adds (include/hsg_cnn_tokens.h): no a * b + c -> fma anywhere in the file
+              "hsg_cnn_tokens.hip": ["-ffp-contract=off"]}
 
 
 def _obj(src, dev=False):

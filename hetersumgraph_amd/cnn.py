@@ -23,6 +23,7 @@ import ctypes
 
 import torch
 
+from . import _lib
 from ._lib import check, load, ptr, stream_of
 from .dense import gemm, splits_for
 
@@ -142,6 +143,140 @@ def sent_cnn(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_i
     wall = stack_taps([w.float() for w in conv_weights])
     return _SentCNN.apply(ids.long().contiguous(), embed_weight.contiguous(), pos_weight.contiguous(), wall,
                           padding_idx, *[b.contiguous() for b in conv_biases])
+
+
+# ---------------------------------------------------------------------------------------------
+# Opt-in (``path_options(HSG_SENT_CNN="dw" | "tokens")``, include/hsg_cnn_tokens.h), for a frozen
+# embedding and position table:
+#   "dw"      today's forward; the weight gradient summed directly from the max windows
+#             (hsg_cnn_tok_dw: no dY, no saved X, no GEMM)
+#   "tokens"  also the forward on the batch's DISTINCT tokens: Y[row] = (E Wall^T)[token] +
+#             (P Wall^T)[position], so the GEMM covers U + L + 1 rows instead of sum_s (len_s + 1)
+MODES = ("0", "dw", "tokens")
+
+
+def sent_cnn_mode():
+    """The value of the ``HSG_SENT_CNN`` switch ("0", "dw" or "tokens"); anything else raises."""
+    mode = _lib.path_option("HSG_SENT_CNN", "0")
+    if mode not in MODES:
+        raise ValueError(f"HSG_SENT_CNN={mode!r}: one of {', '.join(MODES)}")
+    return mode
+
+
+def token_path_ok(ids, embed_weight, pos_weight) -> bool:
+    """The token paths cover this call: a ROCm device, fp32, contiguous tables, a width and a
+    sentence length the kernels take (D % 4 == 0, 7 <= L <= 400), the word embedding and the
+    position table both frozen, and HSG_CHECK_NAN off (its assertions live on today's path)."""
+    from .module.GATLayer import CHECK_NAN
+    if CHECK_NAN or not (ids.is_cuda and embed_weight.is_cuda and pos_weight.is_cuda) or ids.dim() != 2:
+        return False
+    if embed_weight.dtype != torch.float32 or pos_weight.dtype != torch.float32:
+        return False
+    if embed_weight.requires_grad or pos_weight.requires_grad:
+        return False
+    if embed_weight.dim() != 2 or not embed_weight.is_contiguous() or not pos_weight.is_contiguous():
+        return False
+    L, D = ids.shape[1], embed_weight.shape[1]
+    return L <= pos_weight.shape[0] - 1 and bool(load().hsg_cnn_tok_supported(L, D))
+
+
+def _layout_tokens(ids, V, slots):
+    """:func:`_layout` plus the range check of the ids and -- ``slots`` -- the slot map of the
+    batch's distinct tokens (PAD included), all behind the same single read-back.  Returns
+    (length, rowoff, rows, present int32 [V] | None, slot int32 [V] | None, U)."""
+    n, L = ids.shape
+    nz = ids != 0
+    length = nz.sum(1)
+    ar = torch.arange(L, device=ids.device)
+    inner = (nz & (ar.unsqueeze(0) >= length.unsqueeze(1))).any()
+    rowoff = torch.zeros(n + 1, dtype=torch.int32, device=ids.device)
+    torch.cumsum(length + 1, 0, out=rowoff[1:])
+    present = slot = None
+    if slots:
+        present = torch.zeros(V + 1, dtype=torch.int32, device=ids.device)      # [V] flags, then *bad
+        check(load().hsg_cnn_tok_mark(n, L, V, ptr(ids), ptr(present), ptr(present[V:]), stream_of(ids)),
+              "hsg_cnn_tok_mark")
+        slot = torch.cumsum(present[:V], 0, dtype=torch.int32) - 1
+        oob, U = present[V].long(), slot[V - 1].long() + 1
+    else:
+        oob, U = ((ids < 0) | (ids >= V)).any().long(), inner.new_zeros((), dtype=torch.long)
+    rows, inner, oob, U = torch.stack([rowoff[-1].long(), inner.long(), oob, U]).tolist()
+    if oob:
+        raise ValueError(f"sentEncoder: token ids outside the vocabulary [0, {V})")
+    if inner:
+        raise ValueError("sentEncoder: token ids after the first PAD (0) -- padding must be trailing")
+    return length, rowoff, rows, present, slot, U
+
+
+class _SentCNNTokens(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ids, embed_w, pos_w, wall, mode, *bias):
+        lib = load()
+        n, L = ids.shape
+        V, D = embed_w.shape
+        st = stream_of(embed_w)
+        _, rowoff, rows, present, slot, U = _layout_tokens(ids, V, mode == "tokens")
+        if mode == "tokens":
+            Tb = embed_w.new_empty(U + L + 1, D)
+            check(lib.hsg_cnn_tok_table(V, D, U, L, ptr(present), ptr(slot), ptr(embed_w), ptr(pos_w), ptr(Tb), D,
+                                        st), "hsg_cnn_tok_table")
+            TW = embed_w.new_empty(U + L + 1, LDY)
+            gemm(Tb, wall, b_t=True, out=TW[:, :NY])
+            feat = embed_w.new_empty(n, len(HEIGHTS) * CHANNELS)
+            arg = torch.empty(n, len(HEIGHTS) * CHANNELS, dtype=torch.int32, device=ids.device)
+            bptr = (ctypes.c_void_p * len(bias))(*[b.data_ptr() for b in bias])
+            check(lib.hsg_cnn_tok_pool(n, L, V, U, ptr(ids), ptr(rowoff), ptr(slot), ptr(TW), LDY, bptr, ptr(feat),
+                                       ptr(arg), st), "hsg_cnn_tok_pool")
+        else:
+            X = embed_w.new_empty(rows, D)
+            check(lib.hsg_cnn_gather(n, L, D, ptr(ids), ptr(embed_w), ptr(pos_w), ptr(rowoff), rows, ptr(X), st),
+                  "hsg_cnn_gather")
+            feat, arg = _conv_pool(X, n, L, rowoff, wall, bias)
+        ctx.save_for_backward(ids, embed_w, pos_w, rowoff, feat, arg)     # X, Y / Tb, TW end with the forward
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        ids, embed_w, pos_w, rowoff, feat, arg = ctx.saved_tensors
+        lib = load()
+        n, L = ids.shape
+        V, D = embed_w.shape
+        dfeat = dfeat.contiguous()
+        nws = lib.hsg_cnn_tok_dw_ws_floats(n, D)
+        ws = embed_w.new_empty(nws)
+        dwall = embed_w.new_empty(NY, D)
+        db = embed_w.new_empty(len(HEIGHTS) * CHANNELS)
+        check(lib.hsg_cnn_tok_dw(n, L, V, D, ptr(ids), ptr(rowoff), ptr(embed_w), ptr(pos_w), ptr(feat), ptr(arg),
+                                 ptr(dfeat), ptr(ws), ptr(dwall), D, ptr(db), stream_of(embed_w)), "hsg_cnn_tok_dw")
+        db = db.view(len(HEIGHTS), CHANNELS)
+        dbias = [db[g] if need else None for g, need in enumerate(ctx.needs_input_grad[5:])]
+        return (None, None, None, dwall if ctx.needs_input_grad[3] else None, None, *dbias)
+
+
+def sent_cnn_tokens(ids, embed_weight, pos_weight, conv_weights, conv_biases, mode="tokens"):
+    """:func:`sent_cnn` for a frozen embedding on the token paths (``mode``: "dw" or "tokens",
+    see above).  The caller has asked :func:`token_path_ok`; the arguments and the result are
+    :func:`sent_cnn`'s.  An id outside the vocabulary raises ``ValueError`` before any table row
+    is read."""
+    if mode not in MODES[1:]:
+        raise ValueError(f"sent_cnn_tokens: mode {mode!r} is not one of {', '.join(MODES[1:])}")
+    if not token_path_ok(ids, embed_weight, pos_weight):
+        raise RuntimeError("sent_cnn_tokens: the call is outside token_path_ok (frozen fp32 tables on a ROCm device)")
+    n, L = ids.shape
+    if n == 0:
+        return embed_weight.new_zeros(0, len(HEIGHTS) * CHANNELS)
+    wall = stack_taps([w.float() for w in conv_weights])
+    return _SentCNNTokens.apply(ids.long().contiguous(), embed_weight, pos_weight, wall, mode,
+                                *[b.contiguous() for b in conv_biases])
+
+
+def sent_cnn_switched(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_idx=None):
+    """:func:`sent_cnn` behind the ``HSG_SENT_CNN`` switch: a token path where it is selected and
+    :func:`token_path_ok` holds, today's path (and its errors) for every other call."""
+    mode = sent_cnn_mode()
+    if mode != "0" and token_path_ok(ids, embed_weight, pos_weight):
+        return sent_cnn_tokens(ids, embed_weight, pos_weight, conv_weights, conv_biases, mode=mode)
+    return sent_cnn(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_idx=padding_idx)
 
 
 class _SentCNNRows(torch.autograd.Function):

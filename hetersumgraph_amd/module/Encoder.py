@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.init as init
 
-from ..cnn import sent_cnn, sent_cnn_rows
+from ..cnn import sent_cnn_mode, sent_cnn_rows, sent_cnn_switched, token_path_ok
 from .PositionEmbedding import get_sinusoid_encoding_table
 
 WORD_PAD = "[PAD]"
@@ -37,9 +37,15 @@ class sentEncoder(nn.Module):
 
     def forward(self, input):
         # input: [n_sent, L] token ids, PAD = 0 (trailing) -> [n_sent, 300]
-        return sent_cnn(input, self.embed.weight, self.position_embedding.weight,
-                        [c.weight for c in self.convs], [c.bias for c in self.convs],
-                        padding_idx=getattr(self.embed, "padding_idx", None))
+        # Opt-in (``path_options(HSG_SENT_CNN="dw" | "tokens")``): with a frozen
+        # embedding, the sparse weight gradient / the forward on the batch's distinct tokens
+        return sent_cnn_switched(input, self.embed.weight, self.position_embedding.weight,
+                                 [c.weight for c in self.convs], [c.bias for c in self.convs],
+                                 padding_idx=getattr(self.embed, "padding_idx", None))
+
+    def takes_token_path(self, input):
+        """True when :meth:`forward` would run ``input`` on a token path (``HSG_SENT_CNN``)."""
+        return sent_cnn_mode() != "0" and token_path_ok(input, self.embed.weight, self.position_embedding.weight)
 
     def forward_rows(self, X, layout, shape):
         """:meth:`forward` from the gathered row matrix on (``X``, ``layout`` from
