@@ -1,8 +1,15 @@
-"""ctypes binding of libhsg.so (the C ABI declared in include/hsg.h).
+"""ctypes binding of libhsg.so (the C ABI declared in include/hsg*.h).
 
 The library is built in-tree (``python -m hetersumgraph_amd.build`` or
 ``__graft_entry__.build()``).  There is deliberately no fallback: if the shared
 object is missing or a call fails, a ``RuntimeError`` is raised.
+
+``ABI`` is the one registry of entry points: header file name -> {function name:
+argtypes}; ``RESTYPE`` names the few functions that do not return ``int``.  ``load()``
+binds from it and nothing else.  The tables are written out (nothing is parsed at
+import time, so the package loads a library without include/ beside it) and
+tests/test_abi_conformance.py holds them against the headers' declarations, parameter
+by parameter.
 """
 from __future__ import annotations
 
@@ -17,64 +24,6 @@ LIB_PATH = os.environ.get("HSG_LIB_PATH") or os.path.join(_HERE, "libhsg.so")   
 HSG_EINVAL = 1001
 HSG_TAU_TABLE = 0
 HSG_TAU_PER_EDGE = 1
-
-# every symbol include/hsg.h declares (checked by tests/test_abi.py)
-EXPORTS = ("hsg_gat_fwd", "hsg_gat_bwd_dst", "hsg_gat_bwd_blocks", "hsg_gat_bwd_src",
-           "hsg_gat_bwd_src_blocks", "hsg_attn_src_logits", "hsg_attn_params_fwd", "hsg_attn_params_fwd_pair", "hsg_attn_params_fwd_pair_seed", "hsg_attn_params_finish_pair", "hsg_attn_params_bwd",
-           "hsg_attn_params_bwd_workspace_floats", "hsg_version", "hsg_gemm_f32", "hsg_gemm_f32_mfma", "hsg_gemm_bf16", "hsg_gemm_workspace_floats", "hsg_gemm_auto_splits", "hsg_gemm_row_tiles", "hsg_ffn_colsums",
-           "hsg_ln_bwd_blocks", "hsg_ln_fwd", "hsg_ln_bwd",
-           "hsg_dropmask_words", "hsg_dropmask_scale", "hsg_dropmask", "hsg_hproj_fwd", "hsg_hproj_dx",
-           "hsg_hproj_dw_chunks", "hsg_hproj_dw", "hsg_hproj_bwd", "hsg_rel_build_workspace_bytes", "hsg_rel_build",
-           "hsg_cnn_taps", "hsg_cnn_gather", "hsg_cnn_pool", "hsg_cnn_pool_bwd",
-           "hsg_ffn_small_supported", "hsg_ffn_small_fwd", "hsg_ffn_small_bwd_blocks", "hsg_ffn_small_bwd",
-           "hsg_attn_params_stage", "hsg_attn_params_finish", "hsg_hproj_fwd_logits_supported",
-           "hsg_hproj_fwd_logits", "hsg_wsplit_dims", "hsg_wsplit", "hsg_gemm_f32_psw", "hsg_dropmask_multi", "hsg_dropmask_multi_wt", "hsg_step_prologue", "hsg_gemm_f32_slabs", "hsg_slab_reduce",
-           "hsg_hproj_wt", "hsg_hproj_fwd_t8_supported", "hsg_hproj_fwd_t8", "hsg_hproj_fwd_mf_supported", "hsg_hproj_fwd_mf", "hsg_kclock_arm",
-           "hsg_kclock_pending", "hsg_seed_advance", "hsg_gat_bwd_dst_noh_supported", "hsg_gat_bwd_dst_noh",
-           "hsg_gat_bwd_dst_g", "hsg_gemm_f32_psw_elug", "hsg_gemm_bf16_psw",
-           "hsg_gemm_bf16_slabs", "hsg_gemm_dw_slabs", "hsg_gemm_dw_tiles", "hsg_gemm_psw_row_tiles", "hsg_gemm_psw_ln",
-           "hsg_gat_bwd_src_g_supported", "hsg_gat_bwd_src_g", "hsg_gemm_psw_elug_rho", "hsg_ffn_small_bwd_gate",
-           "hsg_gat_bwd_src_g_blocks", "hsg_gemm_bf16_psw_io", "hsg_gemm_bf16_psw_elug_rho_a16", "hsg_gemm_psw_elug_rho_gw", "hsg_ln_bwd_dy16",
-           "hsg_gemm_dw_slabs_io", "hsg_ln_fwd_y16", "hsg_gat_bwd_src_g_io", "hsg_rel_work", "hsg_gat_fwd_ws_floats",
-           "hsg_gat_fwd_ws", "hsg_gat_bwd_src_g_ws_floats", "hsg_gat_bwd_src_g_ws", "hsg_gat_fwd_ws16",
-           "hsg_gemm_bf16_psw_elug_rho_x16", "hsg_ln_fwd_x16", "hsg_ln_bwd_x16", "hsg_gemm_f32_psw_plan", "hsg_gemm_f32_psw_route",
-           "hsg_lstm_supported", "hsg_lstm_fwd", "hsg_lstm_bwd")
-
-# every symbol include/hsg_train.h declares (checked by tests/test_train_abi.py)
-TRAIN_EXPORTS = ("hsg_doc_ce", "hsg_mt_tensors_per_launch", "hsg_mt_chunk", "hsg_mt_blocks", "hsg_mt_sqnorm",
-                 "hsg_mt_adam")
-
-# every symbol include/hsg_model.h declares (checked by tests/test_model_abi.py)
-MODEL_EXPORTS = ("hsg_sentfeat_supported", "hsg_sentfeat_rows", "hsg_sentfeat_fwd", "hsg_sentfeat_bwd",
-                 "hsg_docinit_supported", "hsg_docinit_fwd", "hsg_docinit_bwd", "hsg_logits_supported",
-                 "hsg_logits_fwd", "hsg_logits_bwd_blocks", "hsg_logits_bwd")
-
-# every symbol include/hsg_embed.h declares (checked by tests/test_embed_abi.py); bound from
-# EMBED_SIGS, a table of its own next to _SIGS
-EMBED_EXPORTS = ("hsg_embed_supported", "hsg_embed_rows", "hsg_embed_keys", "hsg_embed_piece_rows", "hsg_embed_ws_floats",
-                 "hsg_embed_grad")
-
-# every symbol include/hsg_eval.h declares (checked by tests/test_eval_abi.py); bound from
-# EVAL_SIGS, as EMBED_SIGS
-EVAL_EXPORTS = ("hsg_eval_select_supported", "hsg_eval_select")
-
-# every symbol include/hsg_eval_words.h declares (checked by tests/test_eval_words_abi.py);
-# bound from EVALW_SIGS, as EVAL_SIGS
-EVALW_EXPORTS = ("hsg_eval_words_supported", "hsg_eval_select_words")
-
-# every symbol include/hsg_eval_text.h declares (checked by tests/test_eval_text_abi.py);
-# bound from EVALT_SIGS / EVALT_RESTYPE, as EMBED_SIGS
-EVALT_EXPORTS = ("hsg_eval_text_supported", "hsg_eval_text_word_bound", "hsg_eval_text_workspace_bytes",
-                 "hsg_eval_text_words")
-
-# every symbol include/hsg_resident.h declares (checked by tests/test_resident_abi.py); bound
-# from RES_SIGS, as EVAL_SIGS
-RES_EXPORTS = ("hsg_res_supported", "hsg_res_offsets", "hsg_res_graph", "hsg_res_relation")
-
-# every symbol include/hsg_cnn_tokens.h declares (checked by tests/test_cnn_tokens_abi.py);
-# bound from CNNTOK_SIGS / CNNTOK_RESTYPE, as EMBED_SIGS
-CNNTOK_EXPORTS = ("hsg_cnn_tok_supported", "hsg_cnn_tok_mark", "hsg_cnn_tok_table", "hsg_cnn_tok_pool",
-                  "hsg_cnn_tok_chunk", "hsg_cnn_tok_dw_ws_floats", "hsg_cnn_tok_dw")
 
 HSG_EPI_STORE = 0
 HSG_EPI_RELU_BWD = 1
@@ -132,10 +81,14 @@ _lib = None
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
+_L = ctypes.c_long
+_L64 = ctypes.c_int64
 _RELP = ctypes.POINTER(HsgRel)
 _MTP = ctypes.POINTER(HsgMtTensor)
+_RESP = ctypes.POINTER(HsgResStore)
 
-_SIGS = {
+ABI = {}
+ABI["hsg.h"] = {
     "hsg_gat_fwd": [_RELP, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hsg_gat_bwd_dst": [_RELP, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hsg_gat_bwd_blocks": [_RELP],
@@ -234,12 +187,17 @@ _SIGS = {
     "hsg_lstm_fwd": [_I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _F, _P, ctypes.c_uint32, _P, _I, _P],
     "hsg_lstm_bwd": [_I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _F, _P, ctypes.c_uint32, _P, _P],
     "hsg_gat_bwd_src_g_ws_floats": [_RELP, _I, _I],
+    "hsg_gat_bwd_src_g_ws": [_RELP, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+}
+ABI["hsg_train.h"] = {
     "hsg_doc_ce": [_I, _I, _I, _P, _P, _I, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P],
     "hsg_mt_tensors_per_launch": [],
     "hsg_mt_chunk": [],
     "hsg_mt_blocks": [_MTP, _I],
     "hsg_mt_sqnorm": [_MTP, _I, _P, _P, _P],
     "hsg_mt_adam": [_MTP, _I, _P, _P, _I, _P, _P],
+}
+ABI["hsg_model.h"] = {
     "hsg_sentfeat_supported": [_I, _I, _I, _I],
     "hsg_sentfeat_rows": [],
     "hsg_sentfeat_fwd": [_I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P],
@@ -251,16 +209,8 @@ _SIGS = {
     "hsg_logits_fwd": [_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
     "hsg_logits_bwd_blocks": [_I],
     "hsg_logits_bwd": [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P],
-    "hsg_gat_bwd_src_g_ws":[_RELP, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
 }
-_RESTYPE = {"hsg_version": ctypes.c_char_p, "hsg_wsplit_dims": None, "hsg_gemm_workspace_floats": ctypes.c_size_t,
-            "hsg_attn_params_bwd_workspace_floats": ctypes.c_size_t,
-            "hsg_dropmask_scale": ctypes.c_float,
-            "hsg_rel_build_workspace_bytes": ctypes.c_size_t, "hsg_gat_fwd_ws_floats": ctypes.c_size_t,
-            "hsg_gat_bwd_src_g_ws_floats": ctypes.c_size_t, "hsg_mt_blocks": ctypes.c_size_t}
-
-_L = ctypes.c_long
-EMBED_SIGS = {
+ABI["hsg_embed.h"] = {
     "hsg_embed_supported": [_I],
     "hsg_embed_rows": [_I, _I, _I, _P, _P, _P, _I, _P],
     "hsg_embed_keys": [_I, _I, _I, _L, _P, _P, _P, _L, _P, _P],
@@ -268,30 +218,27 @@ EMBED_SIGS = {
     "hsg_embed_ws_floats": [_L, _I],
     "hsg_embed_grad": [_I, _I, _L, _P, _I, _P, _I, _L, _P, _I, _P, _P, _P],
 }
-EMBED_RESTYPE = {"hsg_embed_ws_floats": ctypes.c_size_t}
-EVAL_SIGS = {
+ABI["hsg_eval.h"] = {
     "hsg_eval_select_supported": [_I, _I],
     "hsg_eval_select": [_I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P],
 }
-EVALW_SIGS = {
+ABI["hsg_eval_words.h"] = {
     "hsg_eval_words_supported": [_I, _I, _I],
     "hsg_eval_select_words": [_I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P],
 }
-_L64 = ctypes.c_int64
-EVALT_SIGS = {
+ABI["hsg_eval_text.h"] = {
     "hsg_eval_text_supported": [_I, _I, _L64],
     "hsg_eval_text_word_bound": [_I, _L64],
     "hsg_eval_text_workspace_bytes": [_I, _I, _L64],
     "hsg_eval_text_words": [_I, _I, _P, _L64, _P, _P, _L64, _P, _P, _P, _P],
 }
-_RESP = ctypes.POINTER(HsgResStore)
-RES_SIGS = {
+ABI["hsg_resident.h"] = {
     "hsg_res_supported": [_I, _L64, _L64, _L64],
     "hsg_res_offsets": [_RESP, _I, _P, _P, _P],
     "hsg_res_graph": [_RESP, _I, _P, _P, _L64, _L64] + [_P] * 11,
     "hsg_res_relation": [_RESP, _I, _I, _P, _P, _L64, _L64, _L64] + [_P] * 11,
 }
-CNNTOK_SIGS = {
+ABI["hsg_cnn_tokens.h"] = {
     "hsg_cnn_tok_supported": [_I, _I],
     "hsg_cnn_tok_mark": [_I, _I, _I, _P, _P, _P, _P],
     "hsg_cnn_tok_table": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
@@ -300,8 +247,20 @@ CNNTOK_SIGS = {
     "hsg_cnn_tok_dw_ws_floats": [_I, _I],
     "hsg_cnn_tok_dw": [_I, _I, _I, _I] + [_P] * 8 + [_P, _I, _P, _P],
 }
-CNNTOK_RESTYPE = {"hsg_cnn_tok_dw_ws_floats": ctypes.c_size_t}
-EVALT_RESTYPE = {"hsg_eval_text_word_bound": ctypes.c_int64, "hsg_eval_text_workspace_bytes": ctypes.c_size_t}
+# every function that does not return int
+RESTYPE = {"hsg_version": ctypes.c_char_p, "hsg_wsplit_dims": None, "hsg_gemm_workspace_floats": ctypes.c_size_t,
+           "hsg_attn_params_bwd_workspace_floats": ctypes.c_size_t,
+           "hsg_dropmask_scale": ctypes.c_float,
+           "hsg_rel_build_workspace_bytes": ctypes.c_size_t, "hsg_gat_fwd_ws_floats": ctypes.c_size_t,
+           "hsg_gat_bwd_src_g_ws_floats": ctypes.c_size_t, "hsg_mt_blocks": ctypes.c_size_t,
+           "hsg_embed_ws_floats": ctypes.c_size_t,
+           "hsg_eval_text_word_bound": ctypes.c_int64, "hsg_eval_text_workspace_bytes": ctypes.c_size_t,
+           "hsg_cnn_tok_dw_ws_floats": ctypes.c_size_t}
+
+
+def exports(header):
+    """The names one header declares (``exports("hsg_train.h")``), in table order."""
+    return tuple(ABI[header])
 
 
 def load():
@@ -314,27 +273,11 @@ def load():
             f"libhsg.so not found at {LIB_PATH}: build it with `python -m hetersumgraph_amd.build` "
             "(hetersumgraph_amd has no CPU fallback for the WSWGAT hot path)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, args in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = _RESTYPE.get(name, ctypes.c_int)
-    for name, args in EMBED_SIGS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = EMBED_RESTYPE.get(name, ctypes.c_int)
-    for sigs in (EVAL_SIGS, EVALW_SIGS, RES_SIGS):
+    for sigs in ABI.values():
         for name, args in sigs.items():
             fn = getattr(lib, name)
             fn.argtypes = args
-            fn.restype = ctypes.c_int
-    for name, args in EVALT_SIGS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = EVALT_RESTYPE.get(name, ctypes.c_int)
-    for name, args in CNNTOK_SIGS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = CNNTOK_RESTYPE.get(name, ctypes.c_int)
+            fn.restype = RESTYPE.get(name, ctypes.c_int)
     _lib = lib
     return lib
 

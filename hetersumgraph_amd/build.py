@@ -25,12 +25,14 @@ OBJDIR = os.path.join(ROOT, "build", "obj")
 DEV_OUT = os.path.join(HERE, "libhsg_dev.so")
 DEV_OBJDIR = os.path.join(ROOT, "build", "obj_dev")
 ARCH = os.environ.get("HSG_OFFLOAD_ARCH", "gfx950")
-HEADERS = [os.path.join(ROOT, "include", h) for h in ("hsg.h", "hsg_train.h", "hsg_model.h", "hsg_embed.h", "hsg_eval.h", "hsg_eval_words.h", "hsg_eval_text.h", "hsg_resident.h", "hsg_cnn_tokens.h")] + [os.path.join(HERE, "csrc", h) for h in
-                                                      ("hsg_rng.h", "hsg_wsplit.h", "hsg_dev.h", "hsg_wave.h")]
 # host-only graph builder (no HIP runtime: usable in DataLoader workers)
 HOST_SOURCES = [os.path.join(HERE, "csrc", "hsg_graphbuild.cpp")]
 HOST_HEADERS = [os.path.join(ROOT, "include", "hsg_graph.h")]
 HOST_OUT = os.path.join(HERE, "libhsg_host.so")
+# every public device header (include/hsg*.h but the host library's) and the kernels' shared ones
+HEADERS = [os.path.join(ROOT, "include", h) for h in sorted(os.listdir(os.path.join(ROOT, "include")))
+           if h.startswith("hsg") and h.endswith(".h") and os.path.join(ROOT, "include", h) not in HOST_HEADERS] + \
+          [os.path.join(HERE, "csrc", h) for h in ("hsg_rng.h", "hsg_wsplit.h", "hsg_dev.h", "hsg_wave.h")]
 
 
 def hipcc():

@@ -15,7 +15,8 @@
  *
  * These entry points live in the same libhsg.so as include/hsg.h's, in a header of their
  * own (as include/hsg_embed.h).  This header carries the same two obligations itself: its
- * declarations equal _lib.CNNTOK_EXPORTS (tests/test_cnn_tokens_abi.py), and every entry
+ * declarations equal its entry in the binding's registry, _lib.ABI["hsg_cnn_tokens.h"]
+ * (tests/test_abi_conformance.py), and every entry
  * point below that writes through a pointer has a guard-band case in
  * tests/test_gpu_cnn_tokens_guard.py.
  *

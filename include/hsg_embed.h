@@ -7,7 +7,8 @@
  *
  * These entry points live in the same libhsg.so as include/hsg.h's, in a header of their
  * own (as include/hsg_train.h and include/hsg_model.h).  This header carries the same two
- * obligations itself: its declarations equal _lib.EMBED_EXPORTS (tests/test_embed_abi.py),
+ * obligations itself: its declarations equal its entry in the binding's registry,
+ * _lib.ABI["hsg_embed.h"] (tests/test_abi_conformance.py),
  * and every entry point below that writes through a pointer has a guard-band case in
  * tests/test_gpu_embed_guard.py.
  *

@@ -6,7 +6,8 @@
  *
  * These entry points live in the same libhsg.so as include/hsg.h's, in a header of their
  * own (as include/hsg_train.h, hsg_model.h and hsg_embed.h).  This header carries the same
- * two obligations itself: its declarations equal _lib.EVAL_EXPORTS (tests/test_eval_abi.py),
+ * two obligations itself: its declarations equal its entry in the binding's registry,
+ * _lib.ABI["hsg_eval.h"] (tests/test_abi_conformance.py),
  * and every entry point below that writes through a pointer has a guard-band case in
  * tests/test_gpu_eval_guard.py.
  *

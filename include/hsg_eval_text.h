@@ -10,8 +10,9 @@
  *
  * These entry points live in the same libhsg.so as include/hsg.h's, in a header of their own
  * (as hsg_train.h, hsg_model.h, hsg_embed.h, hsg_eval.h and hsg_eval_words.h).  This header
- * carries the same two obligations itself: its declarations equal _lib.EVALT_EXPORTS
- * (tests/test_eval_text_abi.py), and every entry point below that writes through a pointer has
+ * carries the same two obligations itself: its declarations equal its entry in the binding's
+ * registry, _lib.ABI["hsg_eval_text.h"] (tests/test_abi_conformance.py), and every entry point
+ * below that writes through a pointer has
  * a guard-band case in tests/test_gpu_eval_text_guard.py.
  *
  * Conventions are hsg.h's: device pointers, caller-owned buffers, no allocation, no

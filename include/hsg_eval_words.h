@@ -11,7 +11,8 @@
  *
  * These entry points live in the same libhsg.so as include/hsg.h's, in a header of their own
  * (as hsg_train.h, hsg_model.h, hsg_embed.h and hsg_eval.h).  This header carries the same two
- * obligations itself: its declarations equal _lib.EVALW_EXPORTS (tests/test_eval_words_abi.py),
+ * obligations itself: its declarations equal its entry in the binding's registry,
+ * _lib.ABI["hsg_eval_words.h"] (tests/test_abi_conformance.py),
  * and every entry point below that writes through a pointer has a guard-band case in
  * tests/test_gpu_eval_words_guard.py.
  *

@@ -5,12 +5,10 @@
  * 219-227, 231-244).
  *
  * These entry points live in the same libhsg.so as include/hsg.h's, in a header of their
- * own (as include/hsg_train.h): tests/test_abi.py pins hsg.h's declarations to
- * _lib.EXPORTS and tests/test_guard_coverage.py reads hsg.h for the entry points that
- * need a guard-band case.  This header carries the same two obligations itself: its
- * declarations equal _lib.MODEL_EXPORTS (tests/test_model_abi.py), and every entry point
- * below that writes through a pointer has a guard-band case in
- * tests/test_gpu_model_guard.py.
+ * own (as include/hsg_train.h), and this header carries the same two obligations: its
+ * declarations equal its entry in the binding's registry, _lib.ABI["hsg_model.h"]
+ * (tests/test_abi_conformance.py), and every entry point below that writes through a
+ * pointer has a guard-band case in tests/test_gpu_model_guard.py.
  *
  * Conventions are hsg.h's: device pointers, fp32 row-major matrices with explicit row
  * pitches (ld*, in elements, >= the row width), caller-owned workspaces, no allocation,

@@ -5,8 +5,9 @@
  *
  * These entry points live in the same libhsg.so as include/hsg.h's, in a header of their own
  * (as include/hsg_train.h, hsg_model.h, hsg_embed.h and hsg_eval.h).  This header carries the
- * same two obligations itself: its declarations equal _lib.RES_EXPORTS
- * (tests/test_resident_abi.py), and every entry point below that writes through a pointer has
+ * same two obligations itself: its declarations equal its entry in the binding's registry,
+ * _lib.ABI["hsg_resident.h"] (tests/test_abi_conformance.py, which also holds the two structs
+ * below to their ctypes mirrors), and every entry point below that writes through a pointer has
  * a guard-band case in tests/test_gpu_resident_guard.py.
  *
  * Conventions are hsg.h's: device pointers, caller-owned buffers, no allocation, no

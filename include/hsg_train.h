@@ -3,11 +3,11 @@
  * loss, the gradient norm, and clip + Adam (train.py:115-119, 132-135).
  *
  * These entry points live in the same libhsg.so as include/hsg.h's, but in a header of
- * their own: tests/test_abi.py pins hsg.h's declarations to _lib.EXPORTS and
- * tests/test_guard_coverage.py reads hsg.h for the entry points that need a guard-band
- * case.  This header carries the same two obligations itself: its declarations equal
- * _lib.TRAIN_EXPORTS (tests/test_train_abi.py), and every entry point below that writes
- * through a pointer has a guard-band case in tests/test_gpu_train_guard.py.
+ * their own.  Every public header carries the same two obligations: its declarations
+ * equal, name by name and parameter by parameter, its entry in the binding's registry
+ * (_lib.ABI["hsg_train.h"]; tests/test_abi_conformance.py), and every entry point below
+ * that writes through a pointer has a guard-band case, here in
+ * tests/test_gpu_train_guard.py (tests/test_guard_coverage.py does this for hsg.h).
  *
  * Conventions are hsg.h's: device pointers unless said otherwise, caller-owned
  * workspaces, no allocation, no synchronisation, no global mutable state, `stream` (a

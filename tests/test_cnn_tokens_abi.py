@@ -1,64 +1,19 @@
-"""The C ABI of the sentence CNN's token paths (include/hsg_cnn_tokens.h): libhsg.so exports
-what the header declares, the binding's CNNTOK_EXPORTS equals it and is bound from a table of
-its own (CNNTOK_SIGS), it is disjoint from the other export lists, the host queries answer as
-documented, refusals return HSG_EINVAL before any launch, and every entry point of the header
-that writes through a pointer has a guard-band case in tests/test_gpu_cnn_tokens_guard.py.
-No GPU needed."""
+"""What is specific to the C ABI of the sentence CNN's token paths (include/hsg_cnn_tokens.h):
+its source is built, the host queries answer as documented, refusals return HSG_EINVAL before
+any launch, and every entry point of the header that writes through a pointer has a guard-band
+case in tests/test_gpu_cnn_tokens_guard.py.  Names, exports, signatures and the header's place
+among the build's dependencies are tests/test_abi_conformance.py's.  No GPU needed."""
 import ctypes
 import os
 
-import pytest
+import abi
 
-from test_model_abi import declared_functions
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsg_cnn_tokens.h")
+HEADER = "hsg_cnn_tokens.h"
 
 
-def writable_entry_points():
-    """test_guard_coverage's parser rule, pointed at hsg_cnn_tokens.h."""
-    import test_guard_coverage as cov
-    saved = cov.HEADERS
-    cov.HEADERS = [HEADER]
-    try:
-        return cov.writable_entry_points()
-    finally:
-        cov.HEADERS = saved
-
-
-def test_header_declares_the_bound_symbols():
-    from hetersumgraph_amd import _lib
-    assert declared_functions(HEADER) == sorted(_lib.CNNTOK_EXPORTS)
-    assert set(_lib.CNNTOK_EXPORTS) == set(_lib.CNNTOK_SIGS)
-    assert set(_lib.CNNTOK_RESTYPE) <= set(_lib.CNNTOK_SIGS)
-
-
-def test_export_list_is_disjoint_from_the_others():
-    from hetersumgraph_amd import _lib
-    e = set(_lib.CNNTOK_EXPORTS)
-    for other in (_lib.EXPORTS, _lib.TRAIN_EXPORTS, _lib.MODEL_EXPORTS, _lib.EMBED_EXPORTS, _lib.EVAL_EXPORTS,
-                  _lib.EVALW_EXPORTS, _lib.EVALT_EXPORTS, _lib.RES_EXPORTS):
-        assert not e & set(other)
-    assert not e & set(_lib._SIGS)
-
-
-def test_the_header_is_a_build_dependency_and_the_source_is_built():
+def test_the_source_is_built():
     from hetersumgraph_amd import build
-    assert HEADER in build.HEADERS
     assert any(os.path.basename(s) == "hsg_cnn_tokens.hip" for s in build.SOURCES)
-
-
-def test_library_exports_every_declared_symbol():
-    from hetersumgraph_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.fail("libhsg.so is not built (run python -m hetersumgraph_amd.build)")
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared_functions(HEADER):
-        assert hasattr(lib, name), name
-    bound = _lib.load()
-    for name, args in _lib.CNNTOK_SIGS.items():
-        assert getattr(bound, name).argtypes == args, name
-        assert getattr(bound, name).restype == _lib.CNNTOK_RESTYPE.get(name, ctypes.c_int), name
 
 
 def test_supported_sets_and_host_queries():
@@ -117,7 +72,7 @@ def test_refusals_before_any_launch():
 
 def test_every_writing_entry_point_has_a_guard_case():
     from test_gpu_cnn_tokens_guard import CASES
-    w = writable_entry_points()
+    w = abi.writable_entry_points([HEADER])
     assert "int32_t *present" in w["hsg_cnn_tok_mark"] and "int32_t *bad" in w["hsg_cnn_tok_mark"]
     assert "float *Tb" in w["hsg_cnn_tok_table"]
     assert "float *feat" in w["hsg_cnn_tok_pool"] and "int32_t *arg" in w["hsg_cnn_tok_pool"]

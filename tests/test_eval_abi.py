@@ -1,55 +1,13 @@
-"""The C ABI of the evaluation step's selection (include/hsg_eval.h): libhsg.so exports what
-the header declares, the binding's EVAL_EXPORTS equals it and is bound from a table of its
-own (EVAL_SIGS, not _SIGS), it is disjoint from the other four export lists, the host query
-answers as documented, refusals return HSG_EINVAL before any launch, and every entry point
-of the header that writes through a pointer has a guard-band case in
-tests/test_gpu_eval_guard.py.  No GPU needed."""
-import ctypes
-import os
-
+"""What is specific to the C ABI of the evaluation step's selection (include/hsg_eval.h): the
+host query answers as documented, refusals return HSG_EINVAL before any launch, the Python
+wrapper refuses what it must, and every entry point of the header that writes through a
+pointer has a guard-band case in tests/test_gpu_eval_guard.py.  Names, exports and
+signatures are tests/test_abi_conformance.py's.  No GPU needed."""
 import pytest
 
-from test_model_abi import declared_functions
+import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsg_eval.h")
-
-
-def writable_entry_points():
-    """test_guard_coverage's parser rule, pointed at hsg_eval.h."""
-    import test_guard_coverage as cov
-    saved = cov.HEADERS
-    cov.HEADERS = [HEADER]
-    try:
-        return cov.writable_entry_points()
-    finally:
-        cov.HEADERS = saved
-
-
-def test_header_declares_the_bound_symbols():
-    from hetersumgraph_amd import _lib
-    assert declared_functions(HEADER) == sorted(_lib.EVAL_EXPORTS)
-    assert set(_lib.EVAL_EXPORTS) == set(_lib.EVAL_SIGS)
-
-
-def test_export_list_is_disjoint_from_the_others():
-    from hetersumgraph_amd import _lib
-    e = set(_lib.EVAL_EXPORTS)
-    for other in (_lib.EXPORTS, _lib.TRAIN_EXPORTS, _lib.MODEL_EXPORTS, _lib.EMBED_EXPORTS):
-        assert not e & set(other)
-    assert not e & set(_lib._SIGS) and not e & set(_lib.EMBED_SIGS)
-
-
-def test_library_exports_every_declared_symbol():
-    from hetersumgraph_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.fail("libhsg.so is not built (run python -m hetersumgraph_amd.build)")
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared_functions(HEADER):
-        assert hasattr(lib, name), name
-    bound = _lib.load()
-    for name, args in _lib.EVAL_SIGS.items():
-        assert getattr(bound, name).argtypes == args, name
+HEADER = "hsg_eval.h"
 
 
 def test_supported_limits():
@@ -96,7 +54,7 @@ def test_python_wrapper_refuses_cpu_tensors_and_unsupported_limits():
 
 def test_every_writing_entry_point_has_a_guard_case():
     from test_gpu_eval_guard import CASES
-    w = writable_entry_points()
+    w = abi.writable_entry_points([HEADER])
     for prm in ("int32_t *sel", "int32_t *nsel", "int32_t *doc_counts", "int64_t *totals"):
         assert prm in w["hsg_eval_select"], prm
     assert "hsg_eval_select_supported" not in w

@@ -1,61 +1,11 @@
-"""The C ABI of the word ids from article bytes (include/hsg_eval_text.h): libhsg.so exports
-what the header declares, the binding's EVALT_EXPORTS equals it and is bound from a table of
-its own (EVALT_SIGS), it is disjoint from the other six export lists, the host queries answer
-as documented at each edge, refusals return HSG_EINVAL before any launch, and every entry point
-of the header that writes through a pointer has a guard-band case in
-tests/test_gpu_eval_text_guard.py.  No GPU needed."""
-import ctypes
-import os
+"""What is specific to the C ABI of the word ids from article bytes (include/hsg_eval_text.h):
+the host queries answer as documented at each edge (their 64-bit return types included),
+refusals return HSG_EINVAL before any launch, and every entry point of the header that writes
+through a pointer has a guard-band case in tests/test_gpu_eval_text_guard.py.  Names, exports
+and signatures are tests/test_abi_conformance.py's.  No GPU needed."""
+import abi
 
-import pytest
-
-from test_model_abi import declared_functions
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsg_eval_text.h")
-
-
-def writable_entry_points():
-    """test_guard_coverage's parser rule, pointed at hsg_eval_text.h."""
-    import test_guard_coverage as cov
-    saved = cov.HEADERS
-    cov.HEADERS = [HEADER]
-    try:
-        return cov.writable_entry_points()
-    finally:
-        cov.HEADERS = saved
-
-
-def test_header_declares_the_bound_symbols():
-    from hetersumgraph_amd import _lib
-    assert declared_functions(HEADER) == sorted(_lib.EVALT_EXPORTS)
-    assert set(_lib.EVALT_EXPORTS) == set(_lib.EVALT_SIGS)
-
-
-def test_export_list_is_disjoint_from_the_others():
-    from hetersumgraph_amd import _lib
-    e = set(_lib.EVALT_EXPORTS)
-    for other in (_lib.EXPORTS, _lib.TRAIN_EXPORTS, _lib.MODEL_EXPORTS, _lib.EMBED_EXPORTS, _lib.EVAL_EXPORTS,
-                  _lib.EVALW_EXPORTS):
-        assert not e & set(other)
-    for sigs in (_lib._SIGS, _lib.EMBED_SIGS, _lib.EVAL_SIGS, _lib.EVALW_SIGS):
-        assert not e & set(sigs)
-    for h in ("hsg.h", "hsg_train.h", "hsg_model.h", "hsg_embed.h", "hsg_eval.h", "hsg_eval_words.h"):
-        assert not e & set(declared_functions(os.path.join(ROOT, "include", h))), h
-
-
-def test_library_exports_every_declared_symbol():
-    from hetersumgraph_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.fail("libhsg.so is not built (run python -m hetersumgraph_amd.build)")
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared_functions(HEADER):
-        assert hasattr(lib, name), name
-    bound = _lib.load()
-    for name, args in _lib.EVALT_SIGS.items():
-        assert getattr(bound, name).argtypes == args, name
-    assert bound.hsg_eval_text_word_bound.restype is ctypes.c_int64
-    assert bound.hsg_eval_text_workspace_bytes.restype is ctypes.c_size_t
+HEADER = "hsg_eval_text.h"
 
 
 def test_host_queries():
@@ -101,7 +51,7 @@ def test_refusals_before_any_launch():
 
 def test_every_writing_entry_point_has_a_guard_case():
     from test_gpu_eval_text_guard import CASES
-    w = writable_entry_points()
+    w = abi.writable_entry_points([HEADER])
     for prm in ("int32_t *word_ptr", "int32_t *word_ids", "void *ws"):
         assert prm in w["hsg_eval_text_words"], prm
     for name in ("hsg_eval_text_supported", "hsg_eval_text_word_bound", "hsg_eval_text_workspace_bytes"):

@@ -1,56 +1,11 @@
-"""The C ABI of the selection on word ids (include/hsg_eval_words.h): libhsg.so exports what
-the header declares, the binding's EVALW_EXPORTS equals it and is bound from a table of its
-own (EVALW_SIGS), it is disjoint from the other five export lists, the host query answers as
-documented at each edge, refusals return HSG_EINVAL before any launch, and every entry point
-of the header that writes through a pointer has a guard-band case in
-tests/test_gpu_eval_words_guard.py.  No GPU needed."""
-import ctypes
-import os
+"""What is specific to the C ABI of the selection on word ids (include/hsg_eval_words.h): the
+host query answers as documented at each edge, refusals return HSG_EINVAL before any launch,
+and every entry point of the header that writes through a pointer has a guard-band case in
+tests/test_gpu_eval_words_guard.py.  Names, exports and signatures are
+tests/test_abi_conformance.py's.  No GPU needed."""
+import abi
 
-import pytest
-
-from test_model_abi import declared_functions
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsg_eval_words.h")
-
-
-def writable_entry_points():
-    """test_guard_coverage's parser rule, pointed at hsg_eval_words.h."""
-    import test_guard_coverage as cov
-    saved = cov.HEADERS
-    cov.HEADERS = [HEADER]
-    try:
-        return cov.writable_entry_points()
-    finally:
-        cov.HEADERS = saved
-
-
-def test_header_declares_the_bound_symbols():
-    from hetersumgraph_amd import _lib
-    assert declared_functions(HEADER) == sorted(_lib.EVALW_EXPORTS)
-    assert set(_lib.EVALW_EXPORTS) == set(_lib.EVALW_SIGS)
-
-
-def test_export_list_is_disjoint_from_the_others():
-    from hetersumgraph_amd import _lib
-    e = set(_lib.EVALW_EXPORTS)
-    for other in (_lib.EXPORTS, _lib.TRAIN_EXPORTS, _lib.MODEL_EXPORTS, _lib.EMBED_EXPORTS, _lib.EVAL_EXPORTS):
-        assert not e & set(other)
-    assert not e & set(_lib._SIGS) and not e & set(_lib.EMBED_SIGS) and not e & set(_lib.EVAL_SIGS)
-    assert not e & set(declared_functions(os.path.join(ROOT, "include", "hsg_eval.h")))
-
-
-def test_library_exports_every_declared_symbol():
-    from hetersumgraph_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.fail("libhsg.so is not built (run python -m hetersumgraph_amd.build)")
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared_functions(HEADER):
-        assert hasattr(lib, name), name
-    bound = _lib.load()
-    for name, args in _lib.EVALW_SIGS.items():
-        assert getattr(bound, name).argtypes == args, name
+HEADER = "hsg_eval_words.h"
 
 
 def test_supported_limits():
@@ -90,7 +45,7 @@ def test_refusals_before_any_launch():
 
 def test_every_writing_entry_point_has_a_guard_case():
     from test_gpu_eval_words_guard import CASES
-    w = writable_entry_points()
+    w = abi.writable_entry_points([HEADER])
     for prm in ("int32_t *sel", "int32_t *nsel", "int32_t *doc_counts", "int64_t *totals"):
         assert prm in w["hsg_eval_select_words"], prm
     assert "hsg_eval_words_supported" not in w

@@ -1,11 +1,9 @@
 """Every entry point of the C ABI that writes through a pointer has a guard-band case
 (tests/test_gpu_guard_bands.py, CASES) or an explicit reason not to (NOT_COVERED).  A new
 entry point fails this test until someone decides where it goes.  No GPU needed."""
-import os
-import re
+import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = [os.path.join(ROOT, "include", h) for h in ("hsg.h", "hsg_graph.h")]
+HEADERS = ["hsg.h", "hsg_graph.h"]
 
 DEV_ONLY = "dev / A-B variant: no Python caller on the product path under default options"
 NOT_COVERED = {
@@ -23,29 +21,9 @@ NOT_COVERED = {
 }
 
 
-def writable_entry_points():
-    """hsg_* functions with a pointer parameter whose pointee is not const (the stream
-    handle aside), from the headers' declarations."""
-    out = {}
-    for path in HEADERS:
-        src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-        src = re.sub(r"//[^\n]*", "", src)
-        for name, params in re.findall(r"\b(hsg_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
-            w = []
-            for prm in params.split(","):
-                prm = " ".join(prm.split())
-                if "*" not in prm or prm.startswith("const ") or prm.endswith("*stream"):
-                    continue
-                w.append(prm)
-            if w:
-                out[name] = w
-    return out
-
-
 def test_parser_sees_the_abi():
-    from test_abi import declared_functions
-    w = writable_entry_points()
-    assert set(w) - {"hsg_graph_count", "hsg_graph_fill"} <= set(declared_functions())
+    w = abi.writable_entry_points(HEADERS)
+    assert set(w) - {"hsg_graph_count", "hsg_graph_fill"} <= set(abi.declared_functions("hsg.h"))
     # spot checks: outputs, arrays of output pointers, const-only and pointer-free functions
     assert "float *out" in w["hsg_gat_fwd"] and "void *out16" in w["hsg_gat_fwd_ws16"]
     assert "float *const *ws" in w["hsg_gemm_dw_slabs"] and "void *const *planes" in w["hsg_wsplit"]
@@ -58,7 +36,7 @@ def test_parser_sees_the_abi():
 
 def test_every_writing_entry_point_has_a_case_or_a_reason():
     from test_gpu_guard_bands import CASES
-    w = writable_entry_points()
+    w = abi.writable_entry_points(HEADERS)
     missing = sorted(n for n in w if n not in CASES and n not in NOT_COVERED)
     assert not missing, f"no guard-band case and no NOT_COVERED reason: {missing}"
     for name, reason in NOT_COVERED.items():

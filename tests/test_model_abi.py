@@ -1,57 +1,11 @@
-"""The C ABI of the model glue (include/hsg_model.h): libhsg.so exports what the header
-declares, the binding's MODEL_EXPORTS equals it, the three export lists are pairwise
-disjoint, refusals return HSG_EINVAL before any launch, and every entry point of the
-header that writes through a pointer has a guard-band case in
-tests/test_gpu_model_guard.py.  No GPU needed."""
-import ctypes
-import os
-import re
+"""What is specific to the C ABI of the model glue (include/hsg_model.h): the supported
+sets and host queries, refusals that return HSG_EINVAL before any launch, and every entry
+point of the header that writes through a pointer has a guard-band case in
+tests/test_gpu_model_guard.py.  Names, exports and signatures are
+tests/test_abi_conformance.py's.  No GPU needed."""
+import abi
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsg_model.h")
-
-
-def declared_functions(path=HEADER):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hsg_[a-z0-9_]+)\s*\(", src)))
-
-
-def writable_entry_points():
-    """test_guard_coverage's parser rule, pointed at hsg_model.h."""
-    import test_guard_coverage as cov
-    saved = cov.HEADERS
-    cov.HEADERS = [HEADER]
-    try:
-        return cov.writable_entry_points()
-    finally:
-        cov.HEADERS = saved
-
-
-def test_header_declares_the_bound_symbols():
-    from hetersumgraph_amd import _lib
-    assert declared_functions() == sorted(_lib.MODEL_EXPORTS)
-    assert set(_lib.MODEL_EXPORTS) <= set(_lib._SIGS)
-
-
-def test_export_lists_are_pairwise_disjoint():
-    from hetersumgraph_amd import _lib
-    a, b, c = set(_lib.EXPORTS), set(_lib.TRAIN_EXPORTS), set(_lib.MODEL_EXPORTS)
-    assert not a & b and not a & c and not b & c
-    assert a | b | c == set(_lib._SIGS)
-    inc = os.path.join(ROOT, "include")
-    assert declared_functions(os.path.join(inc, "hsg.h")) == sorted(a)
-    assert declared_functions(os.path.join(inc, "hsg_train.h")) == sorted(b)
-
-
-def test_library_exports_every_declared_symbol():
-    from hetersumgraph_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.fail("libhsg.so is not built (run python -m hetersumgraph_amd.build)")
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared_functions():
-        assert hasattr(lib, name), name
+HEADER = "hsg_model.h"
 
 
 def test_supported_sets_and_host_queries():
@@ -130,7 +84,7 @@ def test_refusals_before_any_launch():
 
 def test_every_writing_entry_point_has_a_guard_case():
     from test_gpu_model_guard import CASES
-    w = writable_entry_points()
+    w = abi.writable_entry_points([HEADER])
     assert "float *S" in w["hsg_sentfeat_fwd"] and "float *X" in w["hsg_sentfeat_fwd"]
     assert "float *dngram" in w["hsg_sentfeat_bwd"] and "float *mean" in w["hsg_docinit_fwd"]
     assert "float *dWd" in w["hsg_docinit_bwd"] and "float *logits" in w["hsg_logits_fwd"]

@@ -1,114 +1,30 @@
-"""The C ABI of the resident document store (include/hsg_resident.h): libhsg.so exports what
-the header declares, the binding's RES_EXPORTS equals it and is bound from a table of its own
-(RES_SIGS), it is disjoint from the other export lists, the ctypes structures mirror the
-header's, the host query answers as documented, refusals return HSG_EINVAL before any launch,
-and every entry point of the header that writes through a pointer has a guard-band case in
-tests/test_gpu_resident_guard.py.  No GPU needed."""
+"""What is specific to the C ABI of the resident document store (include/hsg_resident.h): the
+relation's arrays are the reference's, the family constants are the header's, the host query
+answers as documented, refusals return HSG_EINVAL before any launch, and every entry point of
+the header that writes through a pointer has a guard-band case in
+tests/test_gpu_resident_guard.py.  Names, exports, signatures and the two structures' fields
+are tests/test_abi_conformance.py's.  No GPU needed."""
 import ctypes
 import os
 import re
 
-import pytest
+import abi
 
-from test_model_abi import declared_functions
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsg_resident.h")
-
-
-def writable_entry_points():
-    """test_guard_coverage's parser rule, pointed at hsg_resident.h."""
-    import test_guard_coverage as cov
-    saved = cov.HEADERS
-    cov.HEADERS = [HEADER]
-    try:
-        return cov.writable_entry_points()
-    finally:
-        cov.HEADERS = saved
-
-
-def struct_fields(name):
-    """(type, field) pairs of ``typedef struct <name> {...}`` in the header, in order."""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src, flags=re.S).group(1)
-    out = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r"((?:const )?\w+) (.*)", decl)
-        ty, names = m.group(1), m.group(2)
-        for n in names.split(","):
-            n = n.strip()
-            out.append((ty + (" *" if n.startswith("*") else ""), n.lstrip("*")))
-    return out
-
-
-def test_header_declares_the_bound_symbols():
-    from hetersumgraph_amd import _lib
-    assert declared_functions(HEADER) == sorted(_lib.RES_EXPORTS)
-    assert set(_lib.RES_EXPORTS) == set(_lib.RES_SIGS)
-
-
-def test_export_list_is_disjoint_from_the_others():
-    from hetersumgraph_amd import _lib
-    e = set(_lib.RES_EXPORTS)
-    for other in (_lib.EXPORTS, _lib.TRAIN_EXPORTS, _lib.MODEL_EXPORTS, _lib.EMBED_EXPORTS, _lib.EVAL_EXPORTS,
-                  _lib.EVALW_EXPORTS, _lib.EVALT_EXPORTS):
-        assert not e & set(other)
-    assert not e & set(_lib._SIGS)
-
-
-def test_library_exports_every_declared_symbol():
-    from hetersumgraph_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.fail("libhsg.so is not built (run python -m hetersumgraph_amd.build)")
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared_functions(HEADER):
-        assert hasattr(lib, name), name
-    bound = _lib.load()
-    for name, args in _lib.RES_SIGS.items():
-        assert getattr(bound, name).argtypes == args, name
-
-
-def test_signatures_match_the_header():
-    """Parameter by parameter: pointers are void pointers (the store: a struct pointer), int64_t
-    is c_int64, int is c_int."""
-    from hetersumgraph_amd import _lib
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name, params in re.findall(r"\b(hsg_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
-        want = []
-        for prm in params.split(","):
-            prm = " ".join(prm.split())
-            if prm.startswith("const hsg_res_store *"):
-                want.append(ctypes.POINTER(_lib.HsgResStore))
-            elif "*" in prm:
-                want.append(ctypes.c_void_p)
-            else:
-                want.append({"int": ctypes.c_int, "int64_t": ctypes.c_int64}[prm.rsplit(" ", 1)[0]])
-        assert _lib.RES_SIGS[name] == want, name
+HEADER = "hsg_resident.h"
 
 
 def test_structures_mirror_the_header():
+    """The mirrors' fields are the conformance test's; here: the relation's arrays are, in
+    order, the ones the reference store keeps, and the store embeds two relations."""
     from hetersumgraph_amd import _lib
-    ctype = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}
-    for cname, cls in (("hsg_res_rel", _lib.HsgResRel), ("hsg_res_store", _lib.HsgResStore)):
-        want = []
-        for ty, field in struct_fields(cname):
-            if ty.endswith("*"):
-                want.append((field, ctypes.c_void_p))
-            elif ty == "hsg_res_rel":
-                assert field == "rel[2]"
-                want.append(("rel", _lib.HsgResRel * 2))
-            else:
-                want.append((field, ctype[ty]))
-        assert [(n, t) for n, t in cls._fields_] == want, cname
-    assert [f for _, f in struct_fields("hsg_res_rel")] == list(__import__("resident_ref").REL_ARRAYS)
+    assert [f for _, f in abi.struct_fields(HEADER, "hsg_res_rel")] == list(__import__("resident_ref").REL_ARRAYS)
+    assert [f for f, _ in _lib.HsgResRel._fields_] == list(__import__("resident_ref").REL_ARRAYS)
+    assert abi.struct_fields(HEADER, "hsg_res_store")[-1] == ("hsg_res_rel", "rel[2]")
 
 
 def test_family_constants_match_the_header():
     from hetersumgraph_amd import _lib
-    src = open(HEADER).read()
+    src = open(os.path.join(abi.INCLUDE, HEADER)).read()
     val = lambda n: int(re.search(r"#define %s (\d+)" % n, src).group(1))
     assert (_lib.HSG_RES_NODE, _lib.HSG_RES_EDGE, _lib.HSG_RES_SENT, _lib.HSG_RES_NFAM) == \
         (val("HSG_RES_NODE"), val("HSG_RES_EDGE"), val("HSG_RES_SENT"), val("HSG_RES_NFAM"))
@@ -166,7 +82,7 @@ def test_refusals_before_any_launch():
 
 def test_every_writing_entry_point_has_a_guard_case():
     from test_gpu_resident_guard import CASES
-    w = writable_entry_points()
+    w = abi.writable_entry_points([HEADER])
     assert w["hsg_res_offsets"] == ["int64_t *offs"]
     for prm in ("float *unit", "int64_t *words", "int64_t *position", "int64_t *label", "int64_t *src", "float *edtype"):
         assert prm in w["hsg_res_graph"], prm

@@ -1,56 +1,23 @@
-"""The C ABI of the training-step tail (include/hsg_train.h): libhsg.so exports what the
-header declares, the binding's TRAIN_EXPORTS equals it, include/hsg.h's own set is
-untouched, and every entry point of the header that writes through a pointer has a
-guard-band case in tests/test_gpu_train_guard.py.  No GPU needed."""
+"""What is specific to the C ABI of the training-step tail (include/hsg_train.h):
+include/hsg.h's own set is untouched, the layout numbers and host queries, refusals before
+any launch, and every entry point of the header that writes through a pointer has a
+guard-band case in tests/test_gpu_train_guard.py.  Names, exports and signatures are
+tests/test_abi_conformance.py's.  No GPU needed."""
 import ctypes
-import os
-import re
 
-import pytest
+import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsg_train.h")
-
-
-def declared_functions(path=HEADER):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(hsg_[a-z0-9_]+)\s*\(", src)))
-
-
-def writable_entry_points():
-    """test_guard_coverage's parser rule, pointed at hsg_train.h."""
-    import test_guard_coverage as cov
-    saved = cov.HEADERS
-    cov.HEADERS = [HEADER]
-    try:
-        return cov.writable_entry_points()
-    finally:
-        cov.HEADERS = saved
-
-
-def test_header_declares_the_bound_symbols():
-    from hetersumgraph_amd import _lib
-    assert declared_functions() == sorted(_lib.TRAIN_EXPORTS)
-    assert set(_lib.TRAIN_EXPORTS) <= set(_lib._SIGS)
-    assert not set(_lib.TRAIN_EXPORTS) & set(_lib.EXPORTS)
-
-
-def test_library_exports_every_declared_symbol():
-    from hetersumgraph_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.fail("libhsg.so is not built (run python -m hetersumgraph_amd.build)")
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared_functions():
-        assert hasattr(lib, name), name
+HEADER = "hsg_train.h"
 
 
 def test_hsg_h_is_unchanged():
     """The training tail adds nothing to include/hsg.h: its declarations are still
-    exactly _lib.EXPORTS, and none of the new names is among them."""
+    exactly the registry's for hsg.h, and none of the new names is among them."""
     from hetersumgraph_amd import _lib
-    old = declared_functions(os.path.join(ROOT, "include", "hsg.h"))
-    assert old == sorted(_lib.EXPORTS)
-    assert not set(old) & set(declared_functions())
+    old = abi.declared_functions("hsg.h")
+    assert old == sorted(_lib.exports("hsg.h"))
+    assert not set(old) & set(abi.declared_functions(HEADER))
+    assert not set(old) & set(_lib.exports(HEADER))
 
 
 def test_struct_layout_and_host_queries():
@@ -86,7 +53,7 @@ def test_refusals_before_any_launch():
 
 def test_every_writing_entry_point_has_a_guard_case():
     from test_gpu_train_guard import CASES
-    w = writable_entry_points()
+    w = abi.writable_entry_points([HEADER])
     assert "float *partials" in w["hsg_mt_sqnorm"] and "double *hyper" in w["hsg_mt_sqnorm"]
     assert "float *norm_out" in w["hsg_mt_adam"] and "float *dlogits" in w["hsg_doc_ce"]
     for name in ("hsg_mt_blocks", "hsg_mt_chunk", "hsg_mt_tensors_per_launch"):
