@@ -21,7 +21,7 @@ import torch.nn.utils.rnn as rnn
 
 from . import _lib, head
 from .graph import TableColumn
-from .lstm import native_lstm_ok, sent_lstm
+from .lstm import fused_lstm_ok, native_lstm_ok, sent_lstm
 from .module.Encoder import sentEncoder
 from .module.GAT import WSWGAT
 from .module.GATLayer import CHECK_NAN, TFIDF_TAG
@@ -223,14 +223,17 @@ class HSumGraph(nn.Module):
         each way; the same values move, so the result is the reference's bit for bit.
 
         Opt-in (``path_options(HSG_SENT_LSTM="1")``): the native recurrence kernels of
-        :mod:`hetersumgraph_amd.lstm` where they cover the call."""
+        :mod:`hetersumgraph_amd.lstm` where they cover the call; ``"2"``:
+        the same with packed weights and one weight-gradient kernel per layer."""
         return self.lstm_proj(self._sent_lstm_out(ngram, glen))
 
     def _sent_lstm_out(self, ngram, glen):
         """The LSTM output rows of :meth:`_sent_lstm_rows`, before ``lstm_proj``."""
-        if (ngram.is_cuda and _lib.path_option("HSG_SENT_LSTM", "0") == "1"
-                and native_lstm_ok(ngram, self.lstm)):
+        mode = _lib.path_option("HSG_SENT_LSTM", "0") if ngram.is_cuda else "0"
+        if mode == "1" and native_lstm_ok(ngram, self.lstm):
             return sent_lstm(ngram, glen, self.lstm)
+        if mode == "2" and fused_lstm_ok(ngram, self.lstm):    # packed weights, one dW kernel per layer
+            return sent_lstm(ngram, glen, self.lstm, fused=True)
         n_doc, max_len = len(glen), max(glen)
         key = ("lstm_index", tuple(glen))
         idx = getattr(self, "_lstm_idx", None)

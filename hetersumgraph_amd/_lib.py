@@ -247,6 +247,15 @@ ABI["hsg_cnn_tokens.h"] = {
     "hsg_cnn_tok_dw_ws_floats": [_I, _I],
     "hsg_cnn_tok_dw": [_I, _I, _I, _I] + [_P] * 8 + [_P, _I, _P, _P],
 }
+ABI["hsg_lstm_train.h"] = {
+    "hsg_lstm_train_supported": [_I, _I, _I],
+    "hsg_lstm_pack_layer_offset": [_I, _I, _I, _I],
+    "hsg_lstm_pack_floats": [_I, _I, _I, _I],
+    "hsg_lstm_pack": [_I, _I, _I, _I, _P, _P, _P],
+    "hsg_lstm_dw_chunk": [],
+    "hsg_lstm_dw_ws_floats": [_I, _I, _I],
+    "hsg_lstm_dw": [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P],
+}
 # every function that does not return int
 RESTYPE = {"hsg_version": ctypes.c_char_p, "hsg_wsplit_dims": None, "hsg_gemm_workspace_floats": ctypes.c_size_t,
            "hsg_attn_params_bwd_workspace_floats": ctypes.c_size_t,
@@ -255,7 +264,9 @@ RESTYPE = {"hsg_version": ctypes.c_char_p, "hsg_wsplit_dims": None, "hsg_gemm_wo
            "hsg_gat_bwd_src_g_ws_floats": ctypes.c_size_t, "hsg_mt_blocks": ctypes.c_size_t,
            "hsg_embed_ws_floats": ctypes.c_size_t,
            "hsg_eval_text_word_bound": ctypes.c_int64, "hsg_eval_text_workspace_bytes": ctypes.c_size_t,
-           "hsg_cnn_tok_dw_ws_floats": ctypes.c_size_t}
+           "hsg_cnn_tok_dw_ws_floats": ctypes.c_size_t,
+           "hsg_lstm_pack_layer_offset": ctypes.c_size_t, "hsg_lstm_pack_floats": ctypes.c_size_t,
+           "hsg_lstm_dw_ws_floats": ctypes.c_size_t}
 
 
 def exports(header):

@@ -16,8 +16,18 @@ In train mode the dropout between layers draws its keep-mask from the project's
 counter hash (:mod:`hetersumgraph_amd.rng`, the FFN dropout generator over the
 row-major element index) instead of the vendor RNN's dropout state: one
 ``(seed snapshot, offset)`` per dropped layer output, shared by forward and backward.
+
+``sent_lstm(..., fused=True)`` (C ABI: include/hsg_lstm_train.h, csrc/hsg_lstm_train.hip)
+is the same node with less around the recurrence: one hsg_lstm_pack launch stacks the
+parameters of all layers (instead of a cat, a stack, two adds and a cat per layer), ``h``
+has no zero row to clear, and each layer's ``dW_ih``, ``dW_hh`` and bias gradient are one
+hsg_lstm_dw call -- ``dgates^T [x | h_prev | 1]`` with ``h_prev`` read in place from ``h``
+-- instead of three split-K GEMMs, a gather and a column sum.  Forward and row gradient
+are bitwise those of ``fused=False``.
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -188,6 +198,116 @@ class _SentLSTM(torch.autograd.Function):
         return (dcur, None, None, None) + tuple(grads)
 
 
+def fused_lstm_ok(rows, lstm) -> bool:
+    """Whether ``sent_lstm(..., fused=True)`` covers this call: :func:`native_lstm_ok` plus a
+    shape hsg_lstm_train_supported takes and no more layers than hsg_lstm_pack packs."""
+    if not native_lstm_ok(rows, lstm) or lstm.num_layers > _PACK_MAX_LAYERS:
+        return False
+    return bool(load().hsg_lstm_train_supported(int(lstm.hidden_size), 2 if lstm.bidirectional else 1,
+                                                int(lstm.input_size)))
+
+
+_PACK_MAX_LAYERS = 4                 # HSG_LSTM_PACK_MAX_LAYERS (include/hsg_lstm_train.h)
+
+
+def _packed(params, spec, in0):
+    """hsg_lstm_pack: per layer the views (W_ih, W_hh, bias) of ONE buffer, the values and
+    pitches of :func:`_stacked`, written by one launch."""
+    lib = load()
+    n_layers, ndir, hid, _ = spec
+    M = ndir * 4 * hid
+    buf = params[0].new_empty(lib.hsg_lstm_pack_floats(n_layers, hid, ndir, in0))
+    table = (ctypes.c_void_p * len(params))(*[ptr(q) for q in params])
+    check(lib.hsg_lstm_pack(n_layers, hid, ndir, in0, table, ptr(buf), stream_of(buf)), "hsg_lstm_pack")
+    out = []
+    for layer in range(n_layers):
+        in_l = in0 if layer == 0 else ndir * hid
+        o = lib.hsg_lstm_pack_layer_offset(layer, hid, ndir, in0)
+        out.append((buf[o:o + M * in_l].view(M, in_l),
+                    buf[o + M * in_l:o + M * (in_l + hid)].view(ndir, 4 * hid, hid),
+                    buf[o + M * (in_l + hid):o + M * (in_l + hid + 1)]))
+    return out
+
+
+def _forward_fused(rows, lay, spec, params, draws):
+    """All layers on the packed operands.  Returns per layer (x, wih, whh, h, gates, c, y);
+    ``h`` has exactly n_rows rows (hsg_lstm_dw reads h_prev in place, no zero row)."""
+    lib = load()
+    n_layers, ndir, hid, p = spec
+    n = lay.n_rows
+    x, out = rows, []
+    for layer, (wih, whh, bias) in enumerate(_packed(params, spec, rows.shape[1])):
+        pl = p if layer < n_layers - 1 else 0.0
+        pre = gemm(x, wih, b_t=True, bias=bias, dtype="f32")
+        h = x.new_empty(n, ndir * hid)
+        gates = x.new_empty(n, ndir * 4 * hid)
+        c = x.new_empty(n, ndir * hid)
+        y = x.new_empty(n, ndir * hid) if pl > 0 else None
+        seed, off = draws[layer] if pl > 0 else (None, 0)
+        check(lib.hsg_lstm_fwd(lay.n_docs, n, hid, ndir, ptr(lay.doc_off), ptr(pre), pre.stride(0), ptr(whh), ptr(h),
+                               h.stride(0), ptr(gates), ptr(c), float(pl), ptr(seed), off, ptr(y),
+                               y.stride(0) if y is not None else 0, stream_of(x)), "hsg_lstm_fwd")
+        out.append((x, wih, whh, h, gates, c, y))
+        x = y if y is not None else h
+    return out
+
+
+class _SentLSTMFused(torch.autograd.Function):
+    """:class:`_SentLSTM` with the parameters packed by one launch and each layer's three
+    weight gradients formed by hsg_lstm_dw (include/hsg_lstm_train.h)."""
+
+    @staticmethod
+    def forward(ctx, rows, lay, spec, draws, *params):
+        n_layers = spec[0]
+        with torch.no_grad():
+            layers = _forward_fused(rows, lay, spec, [q.detach() for q in params], draws)
+        saved = []
+        for x, wih, whh, h, gates, c, y in layers:
+            saved += [x, wih, whh, h, gates, c]
+        saved += [d[0] for d in draws if d is not None]
+        ctx.save_for_backward(*saved)
+        ctx.lay, ctx.spec = lay, spec
+        ctx.offsets = [None if d is None else d[1] for d in draws]
+        return layers[n_layers - 1][3]
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = load()
+        lay, (n_layers, ndir, hid, p) = ctx.lay, ctx.spec
+        saved = ctx.saved_tensors
+        seeds = list(saved[6 * n_layers:])
+        seed_of = [None] * n_layers
+        for layer in range(n_layers):
+            if ctx.offsets[layer] is not None:
+                seed_of[layer] = seeds.pop(0)
+        n, G = lay.n_rows, 4 * hid
+        grads = [None] * (4 * n_layers * ndir)
+        ws = dout.new_empty(max(lib.hsg_lstm_dw_ws_floats(n, ndir, saved[6 * layer].shape[1])
+                                for layer in range(n_layers)))
+        dcur = dout.contiguous()
+        for layer in range(n_layers - 1, -1, -1):
+            x, wih, whh, h, gates, c = saved[6 * layer:6 * layer + 6]
+            pl = p if seed_of[layer] is not None else 0.0
+            dg = x.new_empty(n, ndir * G)
+            check(lib.hsg_lstm_bwd(lay.n_docs, n, hid, ndir, ptr(lay.doc_off), ptr(dcur), dcur.stride(0), ptr(gates),
+                                   ptr(c), ptr(whh), float(pl), ptr(seed_of[layer]), ctx.offsets[layer] or 0, ptr(dg),
+                                   stream_of(x)), "hsg_lstm_bwd")
+            in_l = x.shape[1]
+            dwih, dwhh, db = x.new_empty(ndir * G, in_l), x.new_empty(ndir, G, hid), x.new_empty(ndir * G)
+            check(lib.hsg_lstm_dw(lay.n_docs, n, hid, ndir, in_l, ptr(lay.doc_off), ptr(dg), ptr(x), x.stride(0),
+                                  ptr(h), h.stride(0), ptr(ws), ptr(dwih), ptr(dwhh), ptr(db), stream_of(x)),
+                  "hsg_lstm_dw")
+            for d in range(ndir):
+                b = (layer * ndir + d) * 4
+                grads[b], grads[b + 1] = dwih[d * G:(d + 1) * G], dwhh[d]
+                grads[b + 2] = grads[b + 3] = db[d * G:(d + 1) * G]
+            if layer > 0 or ctx.needs_input_grad[0]:
+                dcur = gemm(dg, wih, dtype="f32")
+            else:
+                dcur = None
+        return (dcur, None, None, None) + tuple(grads)
+
+
 def _spec_and_draws(rows, lstm):
     n_layers, ndir, hid = lstm.num_layers, 2 if lstm.bidirectional else 1, lstm.hidden_size
     p = float(lstm.dropout) if lstm.training else 0.0
@@ -199,29 +319,39 @@ def _spec_and_draws(rows, lstm):
     return (n_layers, ndir, hid, p), draws
 
 
-def sent_lstm(rows, glen, lstm):
+def sent_lstm(rows, glen, lstm, fused=False):
     """``lstm`` over the documents' sentence rows: rows [n_rows, in] laid end to end by
     document (``glen``: rows per document, zero allowed) -> [n_rows, ndir * hid], the
     valid rows of the reference's ``pad_packed_sequence(lstm(pack_padded_sequence(...)))``
-    (HiGraph.py:135-141).  No fallback: raises where :func:`native_lstm_ok` is false."""
+    (HiGraph.py:135-141).  No fallback: raises where :func:`native_lstm_ok` is false.
+
+    ``fused=True`` (include/hsg_lstm_train.h): one hsg_lstm_pack launch stacks the
+    parameters of all layers, and each layer's three weight gradients come from one
+    hsg_lstm_dw call instead of three split-K GEMMs, a gather and a column sum.  Output and
+    row gradient are bitwise those of ``fused=False``; the parameter gradients differ by
+    rounding (another summation order).  Raises where :func:`fused_lstm_ok` is false."""
     if not native_lstm_ok(rows, lstm):
         raise RuntimeError("sent_lstm: fp32 ROCm rows and a shape hsg_lstm_supported covers only (no fallback)")
+    if fused and not fused_lstm_ok(rows, lstm):
+        raise RuntimeError("sent_lstm: fused=True for a shape hsg_lstm_train_supported declines (no fallback)")
     lay = doc_layout(glen, rows.device)
     if lay.n_rows != rows.shape[0]:
         raise ValueError(f"sent_lstm: {rows.shape[0]} rows for documents of {lay.n_rows} sentences")
     spec, draws = _spec_and_draws(rows, lstm)
     if lay.n_rows == 0:
         return rows.new_zeros(0, spec[1] * spec[2])
-    return _SentLSTM.apply(rows.contiguous(), lay, spec, draws, *lstm_params(lstm))
+    node = _SentLSTMFused if fused else _SentLSTM
+    return node.apply(rows.contiguous(), lay, spec, draws, *lstm_params(lstm))
 
 
-def sent_lstm_states(rows, glen, lstm):
+def sent_lstm_states(rows, glen, lstm, fused=False):
     """Forward only, for tests and tools: per layer (h, c, gates, (seed, offset) or None)
     exactly as :func:`sent_lstm` computes and saves them."""
-    if not native_lstm_ok(rows, lstm):
+    if not native_lstm_ok(rows, lstm) or (fused and not fused_lstm_ok(rows, lstm)):
         raise RuntimeError("sent_lstm_states: no native path for this call")
     lay = doc_layout(glen, rows.device)
     spec, draws = _spec_and_draws(rows, lstm)
     with torch.no_grad():
-        layers = _forward(rows.contiguous(), lay, spec, [q.detach() for q in lstm_params(lstm)], draws)
+        fwd = _forward_fused if fused else _forward
+        layers = fwd(rows.contiguous(), lay, spec, [q.detach() for q in lstm_params(lstm)], draws)
     return [(hbuf[:lay.n_rows], c, gates, draws[i]) for i, (_, _, _, hbuf, gates, c, _) in enumerate(layers)]

@@ -2,13 +2,17 @@
 spends its time on cfg2 -- synchronised wall time per phase, then the same step
 under torch.profiler for the host/device split.
 
-    python tools/e2e_profile.py [cfg] [--sent-lstm 0|1|ab] [--tail 0|1|ab] [--glue 0|1|ab]
+    python tools/e2e_profile.py [cfg] [--sent-lstm 0|1|2|ab|ab2] [--tail 0|1|ab] [--glue 0|1|ab]
                                 [--embed-train 0|1|ab] [--sent-cnn 0|dw|tokens|ab] [--no-profile]
 
 --sent-lstm selects the sentence LSTM path (path_options(HSG_SENT_LSTM=...): 0 = the
 vendor nn.LSTM, 1 = the native recurrence kernels of hetersumgraph_amd.lstm).  ``ab``
 alternates the two three times in this one process and prints, per leg, one JSON line
-with the phase times plus the LSTM piece's forward and backward timed alone.
+with the phase times plus the LSTM piece's forward and backward timed alone.  2 = the
+native kernels with the parameters packed by one launch and one weight-gradient kernel
+per layer (hetersumgraph_amd.lstm.sent_lstm(..., fused=True)); ``ab2`` alternates 1 and 2
+the same way, with --tail, --glue, --embed-train and --sent-cnn (each 0 / 1 / a path name,
+not ab) applied to both legs.
 
 --tail selects the step's tail (train.py:115-135 with --grad_clip at max_grad_norm = 1.0,
 phases ``loss``, ``clip``, ``adam``): 0 = torch cross entropy + sum_nodes,
@@ -57,8 +61,8 @@ from hetersumgraph_amd import optim as hoptim  # noqa: E402
 
 ARGS = sys.argv[1:]
 SENT_LSTM = ARGS[ARGS.index("--sent-lstm") + 1] if "--sent-lstm" in ARGS else "0"
-if SENT_LSTM not in ("0", "1", "ab"):
-    sys.exit("--sent-lstm takes 0, 1 or ab")
+if SENT_LSTM not in ("0", "1", "2", "ab", "ab2"):
+    sys.exit("--sent-lstm takes 0, 1, 2, ab or ab2")
 TAIL = ARGS[ARGS.index("--tail") + 1] if "--tail" in ARGS else None
 if TAIL not in (None, "0", "1", "ab"):
     sys.exit("--tail takes 0, 1 or ab")
@@ -71,9 +75,9 @@ if EMBED_TRAIN not in (None, "0", "1", "ab"):
 SENT_CNN = ARGS[ARGS.index("--sent-cnn") + 1] if "--sent-cnn" in ARGS else None
 if SENT_CNN not in (None, "0", "dw", "tokens", "ab"):
     sys.exit("--sent-cnn takes 0, dw, tokens or ab")
-if [TAIL, SENT_LSTM, GLUE, EMBED_TRAIN, SENT_CNN].count("ab") > 1:
+if [TAIL, SENT_LSTM.replace("ab2", "ab"), GLUE, EMBED_TRAIN, SENT_CNN].count("ab") > 1:
     sys.exit("one of --sent-lstm, --tail, --glue, --embed-train and --sent-cnn can be ab")
-PROFILE = "--no-profile" not in ARGS and "ab" not in (SENT_LSTM, TAIL, GLUE, EMBED_TRAIN, SENT_CNN)
+PROFILE = "--no-profile" not in ARGS and "ab" not in (SENT_LSTM.replace("ab2", "ab"), TAIL, GLUE, EMBED_TRAIN, SENT_CNN)
 POS = [a for i, a in enumerate(ARGS)
        if not a.startswith("--") and (i == 0 or ARGS[i - 1] not in ("--sent-lstm", "--tail", "--glue", "--embed-train",
                                                                     "--sent-cnn"))]
@@ -218,8 +222,8 @@ def token_counts():
     return u, int((words != 0).sum()) + words.shape[0], words.shape[0]
 
 
-def leg(mode):
-    with _lib.path_options(HSG_SENT_LSTM=mode):
+def leg(mode, **others):
+    with _lib.path_options(HSG_SENT_LSTM=mode, **others):
         for _ in range(3):
             step(0)
         T.clear()
@@ -306,6 +310,15 @@ if SENT_LSTM == "ab":
     for rep in range(3):
         for mode in ("0", "1"):
             print(json.dumps({"rep": rep, "HSG_SENT_LSTM": mode, **leg(mode)}), flush=True)
+    sys.exit(0)
+if SENT_LSTM == "ab2":
+    others = dict(**({} if GLUE is None else {"HSG_MODEL_GLUE": GLUE}),
+                  **({} if EMBED_TRAIN is None else {"HSG_WORD_EMBED": EMBED_TRAIN}),
+                  **({} if SENT_CNN is None else {"HSG_SENT_CNN": SENT_CNN}))
+    for rep in range(3):
+        for mode in ("1", "2"):
+            print(json.dumps({"rep": rep, "HSG_SENT_LSTM": mode, "tail_leg": TAIL, **others, **leg(mode, **others)}),
+                  flush=True)
     sys.exit(0)
 _mode = _lib.path_options(HSG_SENT_LSTM=SENT_LSTM, **({} if GLUE is None else {"HSG_MODEL_GLUE": GLUE}),
                           **({} if EMBED_TRAIN is None else {"HSG_WORD_EMBED": EMBED_TRAIN}),
