@@ -42,6 +42,14 @@ def _dev(graph, arr):
     return torch.from_numpy(np.ascontiguousarray(arr)).to(graph.device)
 
 
+def model_view(graph):
+    """The index structures a resident batch brought along (``ResidentBatch.model_inputs``,
+    include/hsg_resident_model.h), or None: every other graph, and a resident batch whose
+    columns were written since.  With a view the forward takes the sentences' token rows,
+    positions and layouts from it instead of deriving them (and waiting for the device)."""
+    return getattr(graph, "model_inputs", None)
+
+
 def node_ids(graph, column, value):
     """Cached ``filter_nodes(lambda n: n.data[column] == value)`` (ascending ids)."""
     host = {"unit": "unit", "dtype": "ndtype"}[column]
@@ -139,9 +147,10 @@ class HSumGraph(nn.Module):
         """``n_feature_proj(set_snfeature(graph))`` (HiGraph.py:96, 127-132, 141, 160) as one
         native node behind the two encoders."""
         snode_id = node_ids(graph, "dtype", 1.0)
+        view = model_view(graph)
         ngram_feature = self._ngram(graph, snode_id)
-        snode_pos = graph.ndata["position"][snode_id].view(-1)
-        lstm_rows = self._sent_lstm_out(ngram_feature, sentence_counts(graph))
+        snode_pos = graph.ndata["position"][snode_id].view(-1) if view is None else view.sent_pos
+        lstm_rows = self._sent_lstm_out(ngram_feature, sentence_counts(graph), view)
         return head.sent_features(ngram_feature, snode_pos, self.sent_pos_embed.weight, lstm_rows,
                                   self.cnn_proj, self.lstm_proj, self.n_feature_proj)
 
@@ -179,7 +188,8 @@ class HSumGraph(nn.Module):
         if not (_lib.path_option("HSG_WORD_EMBED", "0") == "1" and graph.device.type == "cuda"
                 and native_embed_ok(self._embed, self.ngram_enc)):
             return None
-        ids = graph.ndata["words"][node_ids(graph, "dtype", 1.0)]
+        view = model_view(graph)
+        ids = graph.ndata["words"][node_ids(graph, "dtype", 1.0)] if view is None else view.sent_ids
         n_pos = self.ngram_enc.position_embedding.weight.shape[0]
         if ids.dim() != 2 or ids.shape[0] == 0 or not 7 <= ids.shape[1] <= n_pos - 1:
             return None                      # today's path states what is wrong with the batch
@@ -189,8 +199,10 @@ class HSumGraph(nn.Module):
 
     def _embed_both(self, graph, wid, ids):
         w = self._embed.weight
+        view = model_view(graph)
+        prebuilt = {} if view is None else {"layout": view.layout}     # without a view: today's call as it is
         w_embed, X, layout = embed_batch(w, wid, ids, self.ngram_enc.position_embedding.weight,
-                                         self._embed.padding_idx)
+                                         self._embed.padding_idx, **prebuilt)
         graph._word_embed_rows = (self, w._version, X, layout, tuple(ids.shape))
         return w_embed
 
@@ -200,6 +212,9 @@ class HSumGraph(nn.Module):
         if held is None or held[0] is not self or held[1] != self._embed.weight._version:
             ids = self._word_embed_ids(graph)
             if ids is None:
+                view = model_view(graph)
+                if view is not None:
+                    return self.ngram_enc(view.sent_ids, layout=view.layout)
                 return self.ngram_enc(graph.ndata["words"][snode_id])
             self._embed_both(graph, ids.new_empty(0), ids)          # set_snfeature on its own
             held = graph.__dict__.pop("_word_embed_rows")
@@ -208,7 +223,8 @@ class HSumGraph(nn.Module):
 
     def _sent_cnn_feature(self, graph, snode_id):
         ngram_feature = self._ngram(graph, snode_id)                             # [n_s, 300]
-        snode_pos = graph.ndata["position"][snode_id].view(-1)
+        view = model_view(graph)
+        snode_pos = graph.ndata["position"][snode_id].view(-1) if view is None else view.sent_pos
         cnn_feature = self.cnn_proj(ngram_feature + self.sent_pos_embed(snode_pos))
         return ngram_feature, cnn_feature
 
@@ -216,7 +232,7 @@ class HSumGraph(nn.Module):
         """HiGraph.py:135-142 on the per-document feature list (see _sent_lstm_rows)."""
         return self._sent_lstm_rows(torch.cat(features, dim=0) if len(features) != 1 else features[0], glen)
 
-    def _sent_lstm_rows(self, ngram, glen):
+    def _sent_lstm_rows(self, ngram, glen, view=None):
         """HiGraph.py:135-142 on the documents' sentence rows laid end to end.  The
         padding to [docs, max_len] and the gather of the valid rows back are one index
         scatter and one index gather (positions cached) instead of a copy per document
@@ -225,15 +241,17 @@ class HSumGraph(nn.Module):
         Opt-in (``path_options(HSG_SENT_LSTM="1")``): the native recurrence kernels of
         :mod:`hetersumgraph_amd.lstm` where they cover the call; ``"2"``:
         the same with packed weights and one weight-gradient kernel per layer."""
-        return self.lstm_proj(self._sent_lstm_out(ngram, glen))
+        return self.lstm_proj(self._sent_lstm_out(ngram, glen, view))
 
-    def _sent_lstm_out(self, ngram, glen):
-        """The LSTM output rows of :meth:`_sent_lstm_rows`, before ``lstm_proj``."""
+    def _sent_lstm_out(self, ngram, glen, view=None):
+        """The LSTM output rows of :meth:`_sent_lstm_rows`, before ``lstm_proj``.  ``view``: the
+        batch's model view, whose document layout the native paths take as it is."""
         mode = _lib.path_option("HSG_SENT_LSTM", "0") if ngram.is_cuda else "0"
+        prebuilt = {} if view is None else {"layout": view.doc_layout}  # without a view: today's call as it is
         if mode == "1" and native_lstm_ok(ngram, self.lstm):
-            return sent_lstm(ngram, glen, self.lstm)
+            return sent_lstm(ngram, glen, self.lstm, **prebuilt)
         if mode == "2" and fused_lstm_ok(ngram, self.lstm):    # packed weights, one dW kernel per layer
-            return sent_lstm(ngram, glen, self.lstm, fused=True)
+            return sent_lstm(ngram, glen, self.lstm, fused=True, **prebuilt)
         n_doc, max_len = len(glen), max(glen)
         key = ("lstm_index", tuple(glen))
         idx = getattr(self, "_lstm_idx", None)
@@ -253,7 +271,7 @@ class HSumGraph(nn.Module):
         snode_id = node_ids(graph, "dtype", 1.0)
         ngram_feature, cnn_feature = self._sent_cnn_feature(graph, snode_id)
         glen = sentence_counts(graph)
-        lstm_feature = self._sent_lstm_rows(ngram_feature, glen)
+        lstm_feature = self._sent_lstm_rows(ngram_feature, glen, model_view(graph))
         return torch.cat([cnn_feature, lstm_feature], dim=1)
 
 

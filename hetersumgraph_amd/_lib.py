@@ -238,6 +238,10 @@ ABI["hsg_resident.h"] = {
     "hsg_res_graph": [_RESP, _I, _P, _P, _L64, _L64] + [_P] * 11,
     "hsg_res_relation": [_RESP, _I, _I, _P, _P, _L64, _L64, _L64] + [_P] * 11,
 }
+ABI["hsg_resident_model.h"] = {
+    "hsg_res_model_supported": [_I, _L64, _L64, _L64],
+    "hsg_res_model": [_RESP, _P, _P, _I, _P, _P, _P, _L64, _L64] + [_P] * 9,
+}
 ABI["hsg_cnn_tokens.h"] = {
     "hsg_cnn_tok_supported": [_I, _I],
     "hsg_cnn_tok_mark": [_I, _I, _I, _P, _P, _P, _P],

@@ -42,6 +42,27 @@ def stack_taps(weights):
     return torch.cat(rows, 0).contiguous()
 
 
+class BatchLayout(tuple):
+    """A prebuilt ``(length, rowoff, rows)`` of :func:`_layout` (the resident store's model view
+    assembles it on the device), checked where it was built: padding is trailing and no id is
+    negative.  ``max_token``: the largest id any batch can hold, for the range check on the host.
+    With one, :func:`sent_cnn` and the "dw" path read nothing back; "tokens" reads back the number
+    of distinct tokens only."""
+
+    def __new__(cls, length, rowoff, rows, max_token):
+        self = super().__new__(cls, (length, rowoff, int(rows)))
+        self.max_token = int(max_token)
+        return self
+
+    def check(self, ids, V=None):
+        n = ids.shape[0]
+        if tuple(self[0].shape) != (n,) or tuple(self[1].shape) != (n + 1,) or self[1].dtype != torch.int32:
+            raise ValueError("sentEncoder: the layout given is not that of these token rows")
+        if V is not None and self.max_token >= V:
+            raise ValueError(f"sentEncoder: token ids outside the vocabulary [0, {V})")
+        return self
+
+
 def _layout(ids):
     """Per-sentence lengths (Encoder.py:57 ``(input != 0).sum``), rowoff [n+1] int32 and
     the total row count (one host sync).  Padding must be trailing: the reference gives
@@ -87,12 +108,12 @@ def _dbias(dfeat, feat, needed):
 
 class _SentCNN(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, embed_w, pos_w, wall, padding_idx, *bias):
+    def forward(ctx, ids, embed_w, pos_w, wall, padding_idx, layout, *bias):
         lib = load()
         n, L = ids.shape
         D = embed_w.shape[1]
         st = stream_of(embed_w)
-        length, rowoff, rows = _layout(ids)
+        length, rowoff, rows = _layout(ids) if layout is None else layout.check(ids)
         X = embed_w.new_empty(rows, D)
         check(lib.hsg_cnn_gather(n, L, D, ptr(ids), ptr(embed_w), ptr(pos_w), ptr(rowoff), rows, ptr(X), st),
               "hsg_cnn_gather")
@@ -119,15 +140,17 @@ class _SentCNN(torch.autograd.Function):
             d_embed = X.new_zeros(ctx.n_embed, D).index_add_(0, tok, dX)
             if ctx.padding_idx is not None:
                 d_embed[ctx.padding_idx] = 0                  # nn.Embedding(padding_idx=...) semantics
-        dbias = _dbias(dfeat, feat, ctx.needs_input_grad[5:])
-        return (None, d_embed, None, dwall, None, *dbias)
+        dbias = _dbias(dfeat, feat, ctx.needs_input_grad[6:])
+        return (None, d_embed, None, dwall, None, None, *dbias)
 
 
-def sent_cnn(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_idx=None):
+def sent_cnn(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_idx=None, layout=None):
     """Encoder.py:56-76 forward on the HIP path: ids [n, L] int64 (PAD = 0, trailing),
     embed_weight [V, D] (``padding_idx``: the embedding row that gets no gradient, as
     nn.Embedding), pos_weight [sent_max_len+1, D] (row 0 = padding position),
-    conv_weights / conv_biases of the six Conv2d(1, 50, (h, D)).  Returns [n, 300]."""
+    conv_weights / conv_biases of the six Conv2d(1, 50, (h, D)).  Returns [n, 300].
+    ``layout``: a :class:`BatchLayout` of ``ids`` in place of the one computed (and read back)
+    here."""
     if not ids.is_cuda or embed_weight.dtype != torch.float32:
         raise RuntimeError("hetersumgraph_amd sentence CNN runs only on a ROCm device in fp32 (no CPU fallback)")
     n, L = ids.shape
@@ -142,7 +165,7 @@ def sent_cnn(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_i
         return embed_weight.new_zeros(0, len(HEIGHTS) * CHANNELS)
     wall = stack_taps([w.float() for w in conv_weights])
     return _SentCNN.apply(ids.long().contiguous(), embed_weight.contiguous(), pos_weight.contiguous(), wall,
-                          padding_idx, *[b.contiguous() for b in conv_biases])
+                          padding_idx, layout, *[b.contiguous() for b in conv_biases])
 
 
 # ---------------------------------------------------------------------------------------------
@@ -210,14 +233,25 @@ def _layout_tokens(ids, V, slots):
 
 class _SentCNNTokens(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, embed_w, pos_w, wall, mode, *bias):
+    def forward(ctx, ids, embed_w, pos_w, wall, mode, layout, *bias):
         lib = load()
         n, L = ids.shape
         V, D = embed_w.shape
         st = stream_of(embed_w)
-        _, rowoff, rows, present, slot, U = _layout_tokens(ids, V, mode == "tokens")
+        if layout is None:
+            _, rowoff, rows, present, slot, U = _layout_tokens(ids, V, mode == "tokens")
+            Tb = embed_w.new_empty(U + L + 1, D) if mode == "tokens" else None
+        else:
+            # the range check is the host's.  U, which sizes the token table, stays a read-back:
+            # sizing it by an upper bound kept with the store measured slower
+            _, rowoff, rows = layout.check(ids, V)
+            if mode == "tokens":
+                present = torch.zeros(V + 1, dtype=torch.int32, device=ids.device)
+                check(lib.hsg_cnn_tok_mark(n, L, V, ptr(ids), ptr(present), ptr(present[V:]), st), "hsg_cnn_tok_mark")
+                slot = torch.cumsum(present[:V], 0, dtype=torch.int32) - 1
+                U = int(slot[V - 1]) + 1
+                Tb = embed_w.new_empty(U + L + 1, D)
         if mode == "tokens":
-            Tb = embed_w.new_empty(U + L + 1, D)
             check(lib.hsg_cnn_tok_table(V, D, U, L, ptr(present), ptr(slot), ptr(embed_w), ptr(pos_w), ptr(Tb), D,
                                         st), "hsg_cnn_tok_table")
             TW = embed_w.new_empty(U + L + 1, LDY)
@@ -249,11 +283,11 @@ class _SentCNNTokens(torch.autograd.Function):
         check(lib.hsg_cnn_tok_dw(n, L, V, D, ptr(ids), ptr(rowoff), ptr(embed_w), ptr(pos_w), ptr(feat), ptr(arg),
                                  ptr(dfeat), ptr(ws), ptr(dwall), D, ptr(db), stream_of(embed_w)), "hsg_cnn_tok_dw")
         db = db.view(len(HEIGHTS), CHANNELS)
-        dbias = [db[g] if need else None for g, need in enumerate(ctx.needs_input_grad[5:])]
-        return (None, None, None, dwall if ctx.needs_input_grad[3] else None, None, *dbias)
+        dbias = [db[g] if need else None for g, need in enumerate(ctx.needs_input_grad[6:])]
+        return (None, None, None, dwall if ctx.needs_input_grad[3] else None, None, None, *dbias)
 
 
-def sent_cnn_tokens(ids, embed_weight, pos_weight, conv_weights, conv_biases, mode="tokens"):
+def sent_cnn_tokens(ids, embed_weight, pos_weight, conv_weights, conv_biases, mode="tokens", layout=None):
     """:func:`sent_cnn` for a frozen embedding on the token paths (``mode``: "dw" or "tokens",
     see above).  The caller has asked :func:`token_path_ok`; the arguments and the result are
     :func:`sent_cnn`'s.  An id outside the vocabulary raises ``ValueError`` before any table row
@@ -266,17 +300,17 @@ def sent_cnn_tokens(ids, embed_weight, pos_weight, conv_weights, conv_biases, mo
     if n == 0:
         return embed_weight.new_zeros(0, len(HEIGHTS) * CHANNELS)
     wall = stack_taps([w.float() for w in conv_weights])
-    return _SentCNNTokens.apply(ids.long().contiguous(), embed_weight, pos_weight, wall, mode,
+    return _SentCNNTokens.apply(ids.long().contiguous(), embed_weight, pos_weight, wall, mode, layout,
                                 *[b.contiguous() for b in conv_biases])
 
 
-def sent_cnn_switched(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_idx=None):
+def sent_cnn_switched(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_idx=None, layout=None):
     """:func:`sent_cnn` behind the ``HSG_SENT_CNN`` switch: a token path where it is selected and
     :func:`token_path_ok` holds, today's path (and its errors) for every other call."""
     mode = sent_cnn_mode()
     if mode != "0" and token_path_ok(ids, embed_weight, pos_weight):
-        return sent_cnn_tokens(ids, embed_weight, pos_weight, conv_weights, conv_biases, mode=mode)
-    return sent_cnn(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_idx=padding_idx)
+        return sent_cnn_tokens(ids, embed_weight, pos_weight, conv_weights, conv_biases, mode=mode, layout=layout)
+    return sent_cnn(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_idx=padding_idx, layout=layout)
 
 
 class _SentCNNRows(torch.autograd.Function):

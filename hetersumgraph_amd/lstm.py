@@ -60,6 +60,20 @@ class DocLayout:
         self.doc_off = off.to(torch.int32).to(device)
         self.prev = torch.stack([p0, p1], 1).to(device)
 
+    @classmethod
+    def prebuilt(cls, glen, doc_off, prev):
+        """The layout of documents of ``glen`` rows from tensors already on the device: what
+        the constructor builds, assembled elsewhere (the resident store's model view)."""
+        lay = cls.__new__(cls)
+        lay.glen = tuple(int(g) for g in glen)
+        lay.n_docs, lay.n_rows = len(lay.glen), int(sum(lay.glen))
+        if tuple(doc_off.shape) != (lay.n_docs + 1,) or tuple(prev.shape) != (lay.n_rows, 2):
+            raise ValueError("DocLayout.prebuilt: doc_off [n_docs + 1] and prev [n_rows, 2] of the documents only")
+        if doc_off.dtype != torch.int32 or prev.dtype != torch.int64 or doc_off.device != prev.device:
+            raise ValueError("DocLayout.prebuilt: int32 doc_off and int64 prev on one device")
+        lay.doc_off, lay.prev = doc_off, prev
+        return lay
+
 
 def doc_layout(glen, device) -> DocLayout:
     """The cached :class:`DocLayout` of a batch, keyed by the ``glen`` tuple (and the
@@ -319,7 +333,7 @@ def _spec_and_draws(rows, lstm):
     return (n_layers, ndir, hid, p), draws
 
 
-def sent_lstm(rows, glen, lstm, fused=False):
+def sent_lstm(rows, glen, lstm, fused=False, layout=None):
     """``lstm`` over the documents' sentence rows: rows [n_rows, in] laid end to end by
     document (``glen``: rows per document, zero allowed) -> [n_rows, ndir * hid], the
     valid rows of the reference's ``pad_packed_sequence(lstm(pack_padded_sequence(...)))``
@@ -329,12 +343,18 @@ def sent_lstm(rows, glen, lstm, fused=False):
     parameters of all layers, and each layer's three weight gradients come from one
     hsg_lstm_dw call instead of three split-K GEMMs, a gather and a column sum.  Output and
     row gradient are bitwise those of ``fused=False``; the parameter gradients differ by
-    rounding (another summation order).  Raises where :func:`fused_lstm_ok` is false."""
+    rounding (another summation order).  Raises where :func:`fused_lstm_ok` is false.
+
+    ``layout``: a :class:`DocLayout` of ``glen`` already on the rows' device
+    (:meth:`DocLayout.prebuilt`); without one the layout is built on the host and cached by
+    ``glen``."""
     if not native_lstm_ok(rows, lstm):
         raise RuntimeError("sent_lstm: fp32 ROCm rows and a shape hsg_lstm_supported covers only (no fallback)")
     if fused and not fused_lstm_ok(rows, lstm):
         raise RuntimeError("sent_lstm: fused=True for a shape hsg_lstm_train_supported declines (no fallback)")
-    lay = doc_layout(glen, rows.device)
+    lay = doc_layout(glen, rows.device) if layout is None else layout
+    if layout is not None and (lay.glen != tuple(int(g) for g in glen) or lay.prev.device != rows.device):
+        raise ValueError("sent_lstm: the layout given is not that of glen on the rows' device")
     if lay.n_rows != rows.shape[0]:
         raise ValueError(f"sent_lstm: {rows.shape[0]} rows for documents of {lay.n_rows} sentences")
     spec, draws = _spec_and_draws(rows, lstm)

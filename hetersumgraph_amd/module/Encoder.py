@@ -35,13 +35,15 @@ class sentEncoder(nn.Module):
         for conv in self.convs:
             init.xavier_normal_(conv.weight.data, gain=np.sqrt(6.0))
 
-    def forward(self, input):
+    def forward(self, input, layout=None):
         # input: [n_sent, L] token ids, PAD = 0 (trailing) -> [n_sent, 300]
         # Opt-in (``path_options(HSG_SENT_CNN="dw" | "tokens")``): with a frozen
-        # embedding, the sparse weight gradient / the forward on the batch's distinct tokens
+        # embedding, the sparse weight gradient / the forward on the batch's distinct tokens.
+        # ``layout``: the sentences' prebuilt row layout (cnn.BatchLayout) instead of the one
+        # computed, and read back, from ``input``
         return sent_cnn_switched(input, self.embed.weight, self.position_embedding.weight,
                                  [c.weight for c in self.convs], [c.bias for c in self.convs],
-                                 padding_idx=getattr(self.embed, "padding_idx", None))
+                                 padding_idx=getattr(self.embed, "padding_idx", None), layout=layout)
 
     def takes_token_path(self, input):
         """True when :meth:`forward` would run ``input`` on a token path (``HSG_SENT_CNN``)."""

@@ -15,6 +15,14 @@ inside a batch every document's slice holds the document's own relation plus fiv
 offsets (node, edge, source rank, destination rank, typed edge).  tests/resident_ref.py
 restates the assembly in numpy and pins it against ``graph.batch`` and the relation oracle.
 
+The store also hands the model its index structures with the batch (the *model view*,
+include/hsg_resident_model.h): the sentence node list, the sentences' token rows with their CNN
+row layout, the LSTM's document layout, the loss's document offsets and the tf-idf table index
+are functions of the picked documents too.  They are validated once per document at build and
+assembled by one more launch per batch, so the model's forward starts without the host-built
+indices (and the host waits) it otherwise begins with.  ``model_view=False`` is the batch
+without it.
+
 There is no fallback: a CPU device, a pick outside the store or a batch beyond
 ``hsg_res_supported`` raises.  Changing a dataset after its store was built is the caller's
 business (the store does not look at the dataset again).
@@ -34,6 +42,8 @@ from .relation import PIECE_MIN, PIECE_MULT
 NODE, EDGE, SENT, NFAM = _lib.HSG_RES_NODE, _lib.HSG_RES_EDGE, _lib.HSG_RES_SENT, _lib.HSG_RES_NFAM
 SRC, DST, TYP = _lib.HSG_RES_SRC, _lib.HSG_RES_DST, _lib.HSG_RES_TYP
 I32_MAX = 2 ** 31 - 1
+VIEW_KEYS = (("nodes", "unit", 0.0), ("nodes", "dtype", 1.0), "sent_counts", "tfidf_index", "sent_doc_off")
+VIEW_COLUMNS = ("unit", "dtype", "tffrac", "words", "id", "label", "position")
 REL_ARRAYS = ("indptr", "src", "tf", "eid", "phantom", "cindptr", "cdst", "cperm", "src_nodes", "dst_nodes")
 
 
@@ -80,6 +90,59 @@ def doc_counts(doc):
     return cnt, longest
 
 
+def sentence_layout(words):
+    """Host statement of ``cnn._layout`` for one document's token rows [N, L]: (length [N],
+    the exclusive prefix of ``length + 1`` [N], the row count, whether a non-zero token follows
+    a PAD)."""
+    words = np.asarray(words)
+    nz = words != 0
+    length = nz.sum(1).astype(np.int64)
+    inner = bool((nz & (np.arange(words.shape[1])[None, :] >= length[:, None])).any())
+    pre = np.zeros(len(length), np.int64)
+    np.cumsum(length[:-1] + 1, out=pre[1:])
+    return length, pre, int((length + 1).sum()), inner
+
+
+def view_refusal(doc, no):
+    """Why document ``no`` cannot carry the model view (None: it can)."""
+    words = np.asarray(doc.words)
+    if sentence_layout(words)[3]:
+        return f"document {no}: token ids after the first PAD (0) -- padding must be trailing"
+    if (words < 0).any():
+        return f"document {no}: a negative token id"
+    if not np.array_equal(np.nonzero(np.asarray(doc.ndtype) == 1)[0], np.asarray(doc.sent_nodes, np.int64)):
+        return f"document {no}: the sentence nodes are not the dtype-1 nodes in ascending order"
+    return None
+
+
+class ModelInputs:
+    """The model view of one resident batch (include/hsg_resident_model.h): device tensors
+    ``sent_nodes``, ``sent_ids``, ``sent_pos``, ``sent_len``, ``rowoff``, ``doc_off``, ``prev``,
+    ``tfidf_index``; host ``rows`` (the CNN's row count), ``bound`` (1 + the sum of the
+    documents' distinct non-zero tokens: at least the batch's distinct tokens, PAD included)
+    and ``max_token`` (the store's largest token id); ``glen``, the sentences per document."""
+
+    def __init__(self, glen, rows, bound, max_token, **tensors):
+        self.glen, self.rows, self.bound, self.max_token = tuple(glen), int(rows), int(bound), int(max_token)
+        self.__dict__.update(tensors)
+        self._lstm = None
+
+    @property
+    def layout(self):
+        """What ``cnn._layout`` returns for ``sent_ids``, with the largest token id for the
+        range check on the host."""
+        from .cnn import BatchLayout
+        return BatchLayout(self.sent_len, self.rowoff, self.rows, self.max_token)
+
+    @property
+    def doc_layout(self):
+        """The ``lstm.DocLayout`` of the batch, from ``doc_off`` and ``prev``."""
+        if self._lstm is None:
+            from .lstm import DocLayout
+            self._lstm = DocLayout.prebuilt(self.glen, self.doc_off, self.prev)
+        return self._lstm
+
+
 class ResidentBatch(BatchedDGLGraph):
     """A batch assembled by :meth:`DocumentStore.batch`: a ``BatchedDGLGraph`` on the store's
     device whose frames and relations are already there.  The host-side structural views
@@ -89,7 +152,27 @@ class ResidentBatch(BatchedDGLGraph):
     def __init__(self):
         self._h_src = self._h_dst = None
         self._origin = None               # (store, slots) until a structural column is written
+        self._view = None                 # (ModelInputs, the columns it restates with their versions)
         super().__init__()
+
+    @property
+    def model_inputs(self):
+        """The batch's :class:`ModelInputs`, or None: no view was assembled, or a column it
+        restates was written since (by assignment, or in place: the tensor's version moved)."""
+        if self._view is not None:
+            nd = self._nframe.cols
+            if any(nd.get(k) is not t or t._version != ver for k, t, ver in self._view[1]):
+                self._drop_view()
+        return None if self._view is None else self._view[0]
+
+    def _set_view(self, view):
+        nd = self._nframe.cols
+        self._view = (view, [(k, nd[k], nd[k]._version) for k in ("words", "position")])
+
+    def _drop_view(self):
+        self._view = None
+        for key in VIEW_KEYS:
+            self._rel_cache.pop((key, str(self.device)), None)
 
     def _edges(self):
         if self._h_src is None and self._origin is not None:
@@ -134,6 +217,7 @@ class ResidentBatch(BatchedDGLGraph):
 
     def _detach(self):
         """A structural write: the store's host copies no longer describe this graph."""
+        self._drop_view()
         if self._origin is not None:
             self._edges()
             self._origin = None
@@ -143,6 +227,8 @@ class ResidentBatch(BatchedDGLGraph):
         super()._mutated()
 
     def _touch_column(self, key, is_node):
+        if key in VIEW_COLUMNS:
+            self._drop_view()
         if key in ("unit", "dtype", "tffrac"):
             self._detach()
         super()._touch_column(key, is_node)
@@ -170,6 +256,8 @@ def _device(device, allow_cpu=False):
 
 class DocumentStore:
     """Every document of a dataset, on the device (see the module docstring)."""
+
+    MODEL_VIEW = True                 # batch()'s default for ``model_view`` (measured: DESIGN.md §6)
 
     # ------------------------------------------------------------------ build
     def __init__(self, device):
@@ -215,6 +303,9 @@ class DocumentStore:
         cols = {k: [] for k in ("unit", "ndtype", "id", "sent_rank", "words", "label", "src", "dst", "tffrac", "edtype")}
         rels = [{k: [] for k in REL_ARRAYS} for _ in HOT_KINDS]
         self.sent_len = self.label_len = None
+        self.model_view, self.model_view_reason = True, None
+        view = {k: [] for k in ("tok_len", "tok_row")}
+        rows_of, distinct, self.max_token = [], [], 0
         n_seen = 0
         for docs in chunks:
             if not docs:
@@ -257,6 +348,18 @@ class DocumentStore:
                 part["sent_rank"].append(rank)
                 part["words"].append(_narrow(words, np.int32, "words", no).reshape(-1))
                 part["label"].append(_narrow(label, np.uint8, "label", no).reshape(-1))
+                # the model view: per sentence its length and row offset (cnn._layout's rule), per
+                # document the row count and the distinct tokens; a document that cannot carry
+                # the view makes the store decline it, nothing raises here
+                length, pre, n_rows, _ = sentence_layout(words)
+                view["tok_len"].append(length.astype(np.int32))
+                view["tok_row"].append(pre.astype(np.int32))
+                rows_of.append(n_rows)
+                distinct.append(int(np.count_nonzero(np.unique(words))))
+                self.max_token = max(self.max_token, int(words.max()) if words.size else 0)
+                if self.model_view:
+                    self.model_view_reason = view_refusal(doc, no)
+                    self.model_view = self.model_view_reason is None
                 counts.append(cnt)
                 longest.append(lng)
                 bases.append(base.copy())
@@ -289,6 +392,9 @@ class DocumentStore:
         self._host = {k: np.concatenate(v) for k, v in host.items()}
         self._cols = {k: torch.cat(v) for k, v in cols.items()}
         self._rels = [{k: torch.cat(v) for k, v in r.items()} for r in rels]
+        self.rows_of = np.asarray(rows_of, np.int64)                     # [n_docs] CNN rows: sum(length + 1)
+        self.distinct = np.asarray(distinct, np.int64)                   # [n_docs] distinct non-zero tokens
+        self._view_cols = {k: torch.from_numpy(np.concatenate(v)).to(dev) for k, v in view.items()}
         self._starts_d = torch.from_numpy(self.starts).to(dev)
         self._bases_d = torch.from_numpy(self.bases).to(dev)
         p = _lib.ptr
@@ -304,7 +410,8 @@ class DocumentStore:
         return self._docs
 
     def _tensors(self):
-        return list(self._cols.values()) + [t for r in self._rels for t in r.values()] + [self._starts_d, self._bases_d]
+        return list(self._cols.values()) + list(self._view_cols.values()) + \
+            [t for r in self._rels for t in r.values()] + [self._starts_d, self._bases_d]
 
     @property
     def nbytes(self):
@@ -340,9 +447,16 @@ class DocumentStore:
         except KeyError as e:
             raise IndexError(f"document {e.args[0]} is not in the store") from None
 
-    def batch(self, indices):
+    def batch(self, indices, model_view=None):
         """``(G, index)`` as ``graph_collate_fn`` gives them for the same documents: sorted by
-        sentence count (descending, ties in the order given), ``G`` on the device."""
+        sentence count (descending, ties in the order given), ``G`` on the device.
+
+        ``model_view``: None (the store's default, :attr:`MODEL_VIEW`), True or False -- whether
+        the batch carries the model's index structures (``G.model_inputs`` and the entries the
+        model caches on the graph), assembled by one more launch.  A store that declined the
+        view at build (``store.model_view`` False, ``store.model_view_reason``) never attaches
+        it.  False is the batch without it, bit for bit."""
+        view = self.model_view and (self.MODEL_VIEW if model_view is None else bool(model_view))
         slots = self.slots_of(indices)
         B = len(slots)
         if B < 1:
@@ -358,7 +472,20 @@ class DocumentStore:
         L, M = self.sent_len, self.label_len
         with torch.cuda.device(dev):
             # one small pinned copy, not waited for (the pinned block is recycled stream-safely)
-            pick = torch.from_numpy(slots.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+            if view:
+                # the per-document CNN row offsets, summed on the host from the kept counts, ride
+                # behind the pick list in the same pinned copy
+                rowbase = np.zeros(B + 1, np.int64)
+                np.cumsum(self.rows_of[slots], out=rowbase[1:])
+                n_s = int(tot[SENT])
+                if not lib.hsg_res_model_supported(B, n_s, E, int(rowbase[B])):
+                    raise RuntimeError(f"batch of {B} documents, {n_s} sentences, {int(rowbase[B])} token rows: "
+                                       "beyond hsg_res_model_supported")
+                both = torch.from_numpy(np.concatenate([slots, rowbase]).astype(np.int32))
+                both = both.pin_memory().to(dev, non_blocking=True)
+                pick, rowbase_d = both[:B], both[B:]
+            else:
+                pick = torch.from_numpy(slots.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
             offs = new(NFAM * (B + 1), i64)
             st = _lib.stream_of(offs)
             cs = ctypes.byref(self._cstruct)
@@ -396,6 +523,19 @@ class DocumentStore:
                 if need:
                     attach_work_lists(d, ns, ndst, nt)         # today's path, with its read-back
                 G._rel_cache[("rel", kind, str(dev))] = Relation.on_device(kind, ns, ndst, d, E)
+            if view:
+                t = dict(sent_nodes=new(n_s, i64), sent_ids=new((n_s, L), i64), sent_pos=new(n_s, i64),
+                         sent_len=new(n_s, i64), rowoff=new(n_s + 1, i32), doc_off=new(B + 1, i32),
+                         prev=new((n_s, 2), i64), tfidf_index=new(E, i64))
+                _lib.check(lib.hsg_res_model(cs, p(self._view_cols["tok_len"]), p(self._view_cols["tok_row"]), B,
+                                             p(pick), p(offs), p(rowbase_d), n_s, E, *[p(v) for v in t.values()], st),
+                           "hsg_res_model")
+                glen = [int(x) for x in self.counts[slots, SENT]]
+                G._set_view(ModelInputs(glen, rowbase[B], 1 + int(self.distinct[slots].sum()), self.max_token, **t))
+                # under the keys HiGraph._cached uses; the word nodes are the W2S relation's sources
+                words = G._rel_cache[("rel", "W2S", str(dev))].dev["src_nodes"]
+                for key, val in zip(VIEW_KEYS, (words, t["sent_nodes"], glen, t["tfidf_index"], t["doc_off"])):
+                    G._rel_cache[(key, str(dev))] = val
             # the launches above read pick and offs after this returns: the allocator keeps a
             # freed block for later work of the SAME stream, so dropping them here is safe
         if self.eval_words is not None:
@@ -406,13 +546,13 @@ class DocumentStore:
 class ResidentLoader:
     """Iterates ``(G, index)`` like ``DataLoader(dataset, batch_size, shuffle, collate_fn=
     graph_collate_fn)``, from a :class:`DocumentStore`.  The permutation is drawn on the host
-    from ``generator``; ``index`` holds dataset indices."""
+    from ``generator``; ``index`` holds dataset indices; ``model_view`` is :meth:`DocumentStore.batch`'s."""
 
-    def __init__(self, store, batch_size, shuffle=False, generator=None, drop_last=False):
+    def __init__(self, store, batch_size, shuffle=False, generator=None, drop_last=False, model_view=None):
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
         self.store, self.batch_size, self.shuffle = store, int(batch_size), shuffle
-        self.generator, self.drop_last = generator, drop_last
+        self.generator, self.drop_last, self.model_view = generator, drop_last, model_view
 
     def __len__(self):
         n = len(self.store)
@@ -429,5 +569,6 @@ class ResidentLoader:
         return out
 
     def __iter__(self):
+        kw = {} if self.model_view is None else {"model_view": self.model_view}     # None: the store's default
         for idx in self.batches():
-            yield self.store.batch(idx)
+            yield self.store.batch(idx, **kw)

@@ -117,7 +117,7 @@ class _EmbedBatch(torch.autograd.Function):
         return (dE,) + (None,) * 6
 
 
-def embed_batch(weight, wid, ids, pos_weight, padding_idx):
+def embed_batch(weight, wid, ids, pos_weight, padding_idx, layout=None):
     """Both lookups of one batch as ONE autograd node over ``weight [V, D]``:
 
     * ``w_embed [n_w, D] = weight[wid]`` (``hsg_embed_rows``; bitwise ``F.embedding``);
@@ -128,13 +128,14 @@ def embed_batch(weight, wid, ids, pos_weight, padding_idx):
     Returns ``(w_embed, X, (length, rowoff, rows))``; the layout goes on to
     :func:`hetersumgraph_amd.cnn.sent_cnn_rows`.  The backward sums ``dW`` and ``dX`` into
     one dense gradient in the fixed order of hsg_embed.h; row ``padding_idx`` (if not None)
-    is exactly zero, as ``nn.Embedding(padding_idx=...)``."""
+    is exactly zero, as ``nn.Embedding(padding_idx=...)``.  ``layout``: a prebuilt
+    :class:`hetersumgraph_amd.cnn.BatchLayout` of ``ids`` in place of the one computed here."""
     if not weight.is_cuda or weight.dtype != torch.float32:
         raise RuntimeError("hetersumgraph_amd word embedding runs only on a ROCm device in fp32 (no CPU fallback)")
     if not embed_supported(weight.shape[1]):
         raise ValueError(f"word embedding: width {weight.shape[1]} is not a multiple of 4 in the supported range")
     wid = wid.long().contiguous()
     ids = ids.long().contiguous()
-    length, rowoff, rows = _layout(ids)
+    length, rowoff, rows = _layout(ids) if layout is None else layout.check(ids)
     w_embed, X = _EmbedBatch.apply(weight.contiguous(), wid, ids, pos_weight.contiguous(), padding_idx, rowoff, rows)
     return w_embed, X, (length, rowoff, rows)
