@@ -275,44 +275,50 @@ class HSumGraph(nn.Module):
         return torch.cat([cnn_feature, lstm_feature], dim=1)
 
 
+def hdsg_host_layout(unit, nd, src, dst):
+    """The host arrays of :func:`_hdsg_layout` from a graph's ``unit`` / ``ndtype`` node columns
+    and its edge list (numpy): ``(host dict, n_docs)``.  Raises what the reference's loops raise.
+    The resident store runs it once per document (hetersumgraph_amd/resident.py)."""
+    snodes = np.nonzero(nd == 1)[0]
+    dnodes = np.nonzero(nd == 2)[0]
+    supers = np.nonzero(unit == 1)[0]
+    super_rank = np.full(len(unit), -1, np.int64)
+    super_rank[supers] = np.arange(len(supers))
+    s_rank = np.full(len(unit), -1, np.int64)
+    s_rank[snodes] = np.arange(len(snodes))
+    d_rank = np.full(len(unit), -1, np.int64)
+    d_rank[dnodes] = np.arange(len(dnodes))
+    # predecessors of doc nodes that are sentences (HiGraph.py:237)
+    sel = np.nonzero((nd[src] == 1) & (nd[dst] == 2))[0]
+    ps, pd = s_rank[src[sel]], d_rank[dst[sel]]
+    cnt = np.bincount(pd, minlength=len(dnodes))
+    if len(dnodes) and cnt.min() == 0:
+        raise AssertionError("doc_feature_element")    # mean of no sentences is NaN (HiGraph.py:239)
+    doc_of_sent = np.full(len(snodes), -1, np.int64)
+    doc_of_sent[ps] = pd                                 # last write wins, like the dict
+    if (doc_of_sent < 0).any():
+        raise KeyError(int(snodes[np.nonzero(doc_of_sent < 0)[0][0]]))   # snid2dnid lookup
+    # supernode state = init_feature[supernode_id] with sentence rows then doc rows
+    pos = np.zeros(len(supers), np.int64)
+    in_s = s_rank[supers] >= 0
+    pos[in_s] = s_rank[supers[in_s]]
+    pos[~in_s] = len(snodes) + d_rank[supers[~in_s]]
+    host = dict(pair_s=ps, pair_d=pd, n_s=len(snodes), super_pos=pos, sent_super=super_rank[snodes],
+                doc_super=super_rank[dnodes[doc_of_sent]], inv_cnt=(1.0 / np.maximum(cnt, 1)).astype(np.float32))
+    return host, len(dnodes)
+
+
 def _hdsg_layout(graph):
-    """Host bookkeeping of HSumDocGraph.forward (HiGraph.py:191-226, 231-244)."""
+    """Host bookkeeping of HSumDocGraph.forward (HiGraph.py:191-226, 231-244).  A resident
+    batch with the doc view brings the same dict along, assembled on the device
+    (include/hsg_resident_hdsg.h), and nothing is built here."""
     def build():
         g = graph
         g._flush()
-        unit = g.host_column("unit")
-        nd = g.host_column("ndtype")
-        snodes = np.nonzero(nd == 1)[0]
-        dnodes = np.nonzero(nd == 2)[0]
-        supers = np.nonzero(unit == 1)[0]
-        super_rank = np.full(len(unit), -1, np.int64)
-        super_rank[supers] = np.arange(len(supers))
-        s_rank = np.full(len(unit), -1, np.int64)
-        s_rank[snodes] = np.arange(len(snodes))
-        d_rank = np.full(len(unit), -1, np.int64)
-        d_rank[dnodes] = np.arange(len(dnodes))
-        # predecessors of doc nodes that are sentences (HiGraph.py:237)
-        sel = np.nonzero((nd[g._src] == 1) & (nd[g._dst] == 2))[0]
-        ps, pd = s_rank[g._src[sel]], d_rank[g._dst[sel]]
-        cnt = np.bincount(pd, minlength=len(dnodes))
-        if len(dnodes) and cnt.min() == 0:
-            raise AssertionError("doc_feature_element")    # mean of no sentences is NaN (HiGraph.py:239)
-        doc_of_sent = np.full(len(snodes), -1, np.int64)
-        doc_of_sent[ps] = pd                                 # last write wins, like the dict
-        if (doc_of_sent < 0).any():
-            raise KeyError(int(snodes[np.nonzero(doc_of_sent < 0)[0][0]]))   # snid2dnid lookup
-        # supernode state = init_feature[supernode_id] with sentence rows then doc rows
-        pos = np.zeros(len(supers), np.int64)
-        in_s = s_rank[supers] >= 0
-        pos[in_s] = s_rank[supers[in_s]]
-        pos[~in_s] = len(snodes) + d_rank[supers[~in_s]]
-        host = dict(pair_s=ps, pair_d=pd, n_s=len(snodes), super_pos=pos, sent_super=super_rank[snodes],
-                    doc_super=super_rank[dnodes[doc_of_sent]], inv_cnt=(1.0 / np.maximum(cnt, 1)).astype(np.float32))
-        return dict(host=host, pair_s=_dev(g, ps), pair_d=_dev(g, pd),
-                    inv_cnt=_dev(g, (1.0 / np.maximum(cnt, 1)).astype(np.float32)),
-                    n_docs=len(dnodes), super_pos=_dev(g, pos),
-                    sent_super=_dev(g, super_rank[snodes]),
-                    doc_super=_dev(g, super_rank[dnodes[doc_of_sent]]))
+        host, n_docs = hdsg_host_layout(g.host_column("unit"), g.host_column("ndtype"), g._src, g._dst)
+        return dict(host=host, n_docs=n_docs,
+                    **{k: _dev(g, host[k]) for k in ("pair_s", "pair_d", "inv_cnt", "super_pos", "sent_super",
+                                                     "doc_super")})
     return _cached(graph, "hdsg_layout", build)
 
 

@@ -70,6 +70,14 @@ class HsgResStore(ctypes.Structure):
                 ("edtype", ctypes.c_void_p), ("rel", HsgResRel * 2)]
 
 
+class HsgResHdsgCols(ctypes.Structure):
+    """Mirror of ``struct hsg_res_hdsg_cols`` (include/hsg_resident_hdsg.h)."""
+
+    _fields_ = [(k, ctypes.c_void_p) for k in ("dstart", "pstart", "pair_s", "pair_d", "doc_sent", "sent_doc",
+                                               "sent_super", "doc_super", "sent_ptr", "sent_row", "sup_list",
+                                               "inv_cnt", "doc_ptr", "doc_row", "sup_code", "sup_sent", "sup_ptr")]
+
+
 # count families of the resident store (include/hsg_resident.h); q = 0 (W2S), 1 (S2W)
 HSG_RES_NODE, HSG_RES_EDGE, HSG_RES_SENT, HSG_RES_NFAM = 0, 1, 2, 9
 HSG_RES_SRC = lambda q: 3 + 3 * q
@@ -241,6 +249,11 @@ ABI["hsg_resident.h"] = {
 ABI["hsg_resident_model.h"] = {
     "hsg_res_model_supported": [_I, _L64, _L64, _L64],
     "hsg_res_model": [_RESP, _P, _P, _I, _P, _P, _P, _L64, _L64] + [_P] * 9,
+}
+ABI["hsg_resident_hdsg.h"] = {
+    "hsg_res_hdsg_supported": [_I, _L64, _L64, _L64, _L64],
+    # cols (const hsg_res_hdsg_cols *) is bound as a plain pointer: pass ctypes.byref(HsgResHdsgCols)
+    "hsg_res_hdsg": [_RESP, _P, _I, _P, _P, _P, _P, _L64, _L64, _L64, _L64] + [_P] * 19,
 }
 ABI["hsg_cnn_tokens.h"] = {
     "hsg_cnn_tok_supported": [_I, _I],

@@ -77,6 +77,34 @@ class HeadLayout:
         self.sup_sent, self.sup_ptr, self.sup_list = _i32(sup_sent, device), _i32(sup_ptr, device), _i32(sup_list, device)
         self.inv_cnt = torch.as_tensor(inv_cnt, dtype=torch.float32).to(device).contiguous()
 
+    # the int32 lists with their lengths as (n_s, n_docs, n_super, pairs, 1) coefficients
+    INT_LISTS = {"super_src": (0, 0, 1, 0, 0), "doc_ptr": (0, 1, 0, 0, 1), "doc_sent": (0, 0, 0, 1, 0),
+                 "sent_ptr": (1, 0, 0, 0, 1), "sent_doc": (0, 0, 0, 1, 0), "sent_row": (1, 0, 0, 0, 0),
+                 "doc_row": (0, 1, 0, 0, 0), "sent_super": (1, 0, 0, 0, 0), "doc_super": (1, 0, 0, 0, 0),
+                 "sup_sent": (0, 0, 1, 0, 0), "sup_ptr": (0, 0, 1, 0, 1), "sup_list": (1, 0, 0, 0, 0)}
+
+    @classmethod
+    def prebuilt(cls, n_s, n_docs, n_super, inv_cnt, **lists):
+        """A complete layout (``ok``) from index lists already on the device: what the
+        constructor builds, assembled elsewhere (the resident store's doc view,
+        include/hsg_resident_hdsg.h).  ``lists``: every name of :attr:`INT_LISTS`, int32."""
+        lay = cls.__new__(cls)
+        lay.n_s, lay.n_docs, lay.n_super, lay.ok = int(n_s), int(n_docs), int(n_super), True
+        if set(lists) != set(cls.INT_LISTS) or lay.n_s < 1 or lay.n_docs < 1 or lay.n_super != lay.n_s + lay.n_docs:
+            raise ValueError("HeadLayout.prebuilt: every index list of a layout whose supernodes are its "
+                             "sentences and doc nodes")
+        dims = (lay.n_s, lay.n_docs, lay.n_super, lists["doc_sent"].numel(), 1)
+        for k, coef in cls.INT_LISTS.items():
+            t = lists[k]
+            n = sum(c * d for c, d in zip(coef, dims))
+            if t.dtype != torch.int32 or t.device != inv_cnt.device or tuple(t.shape) != (n,) or not t.is_contiguous():
+                raise ValueError(f"HeadLayout.prebuilt: '{k}' is not a contiguous int32 [{n}] on the layout's device")
+            setattr(lay, k, t)
+        if inv_cnt.dtype != torch.float32 or tuple(inv_cnt.shape) != (lay.n_docs,) or not inv_cnt.is_contiguous():
+            raise ValueError("HeadLayout.prebuilt: inv_cnt is not a contiguous float32 [n_docs]")
+        lay.inv_cnt = inv_cnt
+        return lay
+
 
 _SUPPORTED = {}
 

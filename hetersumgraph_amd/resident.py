@@ -23,6 +23,13 @@ assembled by one more launch per batch, so the model's forward starts without th
 indices (and the host waits) it otherwise begins with.  ``model_view=False`` is the batch
 without it.
 
+For multi-document examples the store can hand over HSumDocGraph's doc-side layouts too (the
+*doc view*, include/hsg_resident_hdsg.h: the sentence -> doc pair list, the supernode order, the
+native glue's CSRs and inverse lists), kept per document in local form and assembled by one
+launch; and it keeps the lengths of every segment longer than ``relation.PIECE_MIN``, from which
+the item count of a batch's work lists follows on the host (:func:`work_items`), so
+``hsg_rel_work`` runs without its read-back.  ``doc_view=False`` is the batch without both.
+
 There is no fallback: a CPU device, a pick outside the store or a batch beyond
 ``hsg_res_supported`` raises.  Changing a dataset after its store was built is the caller's
 business (the store does not look at the dataset again).
@@ -88,6 +95,84 @@ def doc_counts(doc):
             longest[q, 0] = np.bincount(dst[typed]).max()
             longest[q, 1] = np.bincount(src[typed]).max()
     return cnt, longest
+
+
+def long_segments(doc, above=PIECE_MIN):
+    """Per hot kind, the lengths of the CSR (by destination) and CSC (by source) segments of one
+    ``synth.DocArrays`` that are longer than ``above``: ``[kind][side]`` int64 arrays.  A piece
+    length is never below ``PIECE_MIN``, so these are all a work list's size depends on."""
+    unit, src, dst = np.asarray(doc.unit), np.asarray(doc.src), np.asarray(doc.dst)
+    out = []
+    for kind in HOT_KINDS:
+        su, du = KINDS[kind]
+        typed = (unit[src] == su) & (unit[dst] == du) if len(src) else np.zeros(0, bool)
+        sides = []
+        for ends in (dst, src):
+            deg = np.bincount(ends[typed]) if typed.any() else np.zeros(0, np.int64)
+            sides.append(deg[deg > above].astype(np.int64))
+        out.append(sides)
+    return out
+
+
+def work_items(n, n_typed, long_lens, piece_min=None, piece_mult=None, kept=PIECE_MIN):
+    """``hsg_rel_work``'s item count on the host, the counterpart of :func:`needs_work_list`:
+    for a CSR / CSC of ``n`` segments over ``n_typed`` edges whose segments longer than ``kept``
+    have the lengths ``long_lens`` (any order), ``n + sum over deg > P of (ceil(deg / P) - 1)``
+    with ``P = max(PIECE_MIN, PIECE_MULT * ceil(n_typed / n))`` -- or 0 when no segment exceeds
+    ``P`` (no list).  Raises when ``piece_min`` is below ``kept``: shorter segments could then
+    be split, and their lengths were not kept."""
+    pmin = int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN))) if piece_min is None else piece_min
+    mult = int(_lib.path_option("HSG_PIECE_MULT", str(PIECE_MULT))) if piece_mult is None else piece_mult
+    if n <= 0 or pmin <= 0:
+        return 0
+    if pmin < kept:
+        raise ValueError(f"work_items: piece_min {pmin} is below the kept threshold {kept}")
+    P = max(pmin, mult * (-(-n_typed // n)))
+    deg = np.asarray(long_lens, np.int64)
+    deg = deg[deg > P]
+    if not len(deg):
+        return 0
+    return int(n + (-(-deg // P) - 1).sum())
+
+
+HDSG_COLUMNS = {  # the doc view's stored columns by family (include/hsg_resident_hdsg.h)
+    "pair": ("pair_s", "pair_d", "doc_sent", "sent_doc"),
+    "sent": ("sent_super", "doc_super", "sent_ptr", "sent_row", "sup_list"),
+    "docn": ("inv_cnt", "doc_ptr", "doc_row"),
+    "sup": ("sup_code", "sup_sent", "sup_ptr"),
+}
+HDSG_DICT = ("pair_s", "pair_d", "super_pos", "sent_super", "doc_super")        # int64: HiGraph._hdsg_layout's
+HDSG_HEAD = ("super_src", "doc_ptr", "doc_sent", "sent_ptr", "sent_doc", "sent_row", "doc_row", "sent_super",
+             "doc_super", "sup_sent", "sup_ptr", "sup_list")                    # int32: head.HeadLayout's
+HDSG_KEYS = ("hdsg_layout", "hdsg_head_layout")
+
+
+def doc_view_local(doc, no):
+    """``(reason, columns)`` of document ``no``: today's host constructions
+    (``HiGraph.hdsg_host_layout``, ``head.HeadLayout``) run on the document alone, as the local
+    columns of include/hsg_resident_hdsg.h -- or why the document cannot carry the doc view."""
+    from .HiGraph import hdsg_host_layout
+    from .head import HeadLayout
+    unit, nd = np.asarray(doc.unit), np.asarray(doc.ndtype)
+    if not (nd == 2).any():
+        return f"document {no}: no doc node (ndtype 2)", None
+    try:
+        h, n_docs = hdsg_host_layout(unit, nd, np.asarray(doc.src, np.int64), np.asarray(doc.dst, np.int64))
+    except AssertionError:
+        return f"document {no}: a doc node without a sentence pair", None
+    except KeyError as e:
+        return f"document {no}: sentence node {e.args[0]} has no doc", None
+    lay = HeadLayout(h["pair_s"], h["pair_d"], h["n_s"], n_docs, h["super_pos"], h["sent_super"], h["doc_super"],
+                     h["inv_cnt"], "cpu")
+    if not lay.ok:
+        return f"document {no}: its supernodes (unit 1) are not exactly its sentence and doc nodes", None
+    i32 = lambda a: np.asarray(a).astype(np.int32)
+    cols = dict(pair_s=i32(h["pair_s"]), pair_d=i32(h["pair_d"]), doc_sent=lay.doc_sent.numpy(),
+                sent_doc=lay.sent_doc.numpy(), sent_super=i32(h["sent_super"]), doc_super=i32(h["doc_super"]),
+                sent_ptr=lay.sent_ptr.numpy()[:-1], sent_row=lay.sent_row.numpy(), sup_list=lay.sup_list.numpy(),
+                inv_cnt=h["inv_cnt"], doc_ptr=lay.doc_ptr.numpy()[:-1], doc_row=lay.doc_row.numpy(),
+                sup_code=lay.super_src.numpy(), sup_sent=lay.sup_sent.numpy(), sup_ptr=lay.sup_ptr.numpy()[:-1])
+    return None, cols
 
 
 def sentence_layout(words):
@@ -171,7 +256,7 @@ class ResidentBatch(BatchedDGLGraph):
 
     def _drop_view(self):
         self._view = None
-        for key in VIEW_KEYS:
+        for key in VIEW_KEYS + HDSG_KEYS:                 # the doc view goes with the rest of the view
             self._rel_cache.pop((key, str(self.device)), None)
 
     def _edges(self):
@@ -258,6 +343,7 @@ class DocumentStore:
     """Every document of a dataset, on the device (see the module docstring)."""
 
     MODEL_VIEW = True                 # batch()'s default for ``model_view`` (measured: DESIGN.md §6)
+    DOC_VIEW = True                   # batch()'s default for ``doc_view`` (measured: DESIGN.md §6)
 
     # ------------------------------------------------------------------ build
     def __init__(self, device):
@@ -306,6 +392,11 @@ class DocumentStore:
         self.model_view, self.model_view_reason = True, None
         view = {k: [] for k in ("tok_len", "tok_row")}
         rows_of, distinct, self.max_token = [], [], 0
+        # the doc view (include/hsg_resident_hdsg.h): per document the local form of the doc-side
+        # index structures; the segments longer than PIECE_MIN, which size a batch's work lists
+        self.doc_view, self.doc_view_reason = True, None
+        hdsg = {k: [] for fam in HDSG_COLUMNS.values() for k in fam}
+        long_lens = [[[], []] for _ in HOT_KINDS]
         n_seen = 0
         for docs in chunks:
             if not docs:
@@ -360,6 +451,14 @@ class DocumentStore:
                 if self.model_view:
                     self.model_view_reason = view_refusal(doc, no)
                     self.model_view = self.model_view_reason is None
+                if self.doc_view:
+                    self.doc_view_reason, local = doc_view_local(doc, no)
+                    self.doc_view = self.doc_view_reason is None
+                    for k, a in (local or {}).items():
+                        hdsg[k].append(a)
+                for q, sides in enumerate(long_segments(doc)):
+                    for side, lens in enumerate(sides):
+                        long_lens[q][side].append(lens)
                 counts.append(cnt)
                 longest.append(lng)
                 bases.append(base.copy())
@@ -395,6 +494,22 @@ class DocumentStore:
         self.rows_of = np.asarray(rows_of, np.int64)                     # [n_docs] CNN rows: sum(length + 1)
         self.distinct = np.asarray(distinct, np.int64)                   # [n_docs] distinct non-zero tokens
         self._view_cols = {k: torch.from_numpy(np.concatenate(v)).to(dev) for k, v in view.items()}
+        # [kind][side]: the kept segment lengths of every document end to end, and where each begins
+        self.long_lens = [[np.concatenate(v) for v in sides] for sides in long_lens]
+        self.long_starts = [[np.concatenate([[0], np.cumsum([len(a) for a in v])]).astype(np.int64) for v in sides]
+                            for sides in long_lens]
+        self.doc_view = self.doc_view and self.model_view
+        if self.doc_view_reason is None and not self.model_view:
+            self.doc_view_reason = "the store declined the model view: " + self.model_view_reason
+        self._hdsg_cols, self._hdsg_cstruct = {}, None
+        if self.doc_view:
+            self.docn = np.asarray([len(a) for a in hdsg["inv_cnt"]], np.int64)      # [n_docs] doc nodes
+            self.pairs = np.asarray([len(a) for a in hdsg["pair_s"]], np.int64)      # [n_docs] sentence -> doc pairs
+            starts = lambda c: torch.from_numpy(np.concatenate([[0], np.cumsum(c)]).astype(np.int64)).to(dev)
+            self._hdsg_cols = {k: torch.from_numpy(np.ascontiguousarray(np.concatenate(v))).to(dev)
+                               for k, v in hdsg.items()}
+            self._hdsg_cols.update(dstart=starts(self.docn), pstart=starts(self.pairs))
+            self._hdsg_cstruct = _lib.HsgResHdsgCols(**{k: _lib.ptr(v) for k, v in self._hdsg_cols.items()})
         self._starts_d = torch.from_numpy(self.starts).to(dev)
         self._bases_d = torch.from_numpy(self.bases).to(dev)
         p = _lib.ptr
@@ -410,7 +525,7 @@ class DocumentStore:
         return self._docs
 
     def _tensors(self):
-        return list(self._cols.values()) + list(self._view_cols.values()) + \
+        return list(self._cols.values()) + list(self._view_cols.values()) + list(self._hdsg_cols.values()) + \
             [t for r in self._rels for t in r.values()] + [self._starts_d, self._bases_d]
 
     @property
@@ -447,7 +562,26 @@ class DocumentStore:
         except KeyError as e:
             raise IndexError(f"document {e.args[0]} is not in the store") from None
 
-    def batch(self, indices, model_view=None):
+    def _long(self, q, side, slots):
+        """The kept segment lengths (CSR: side 0, CSC: side 1) of kind ``q`` of the picked documents."""
+        a, st = self.long_lens[q][side], self.long_starts[q][side]
+        return np.concatenate([a[st[s]:st[s + 1]] for s in slots])
+
+    def _sized_work_list(self, lib, n, indptr, n_typed, items, st):
+        """One side's work list with its item count known on the host: the unchanged
+        ``hsg_rel_work`` into today's buffer, sliced by ``items``; nothing is read back."""
+        pmin = int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN)))
+        mult = int(_lib.path_option("HSG_PIECE_MULT", str(PIECE_MULT)))
+        cap = n + 2 * n_typed // pmin + 1
+        if not n <= items <= cap:
+            raise AssertionError(f"work list of {items} items for {n} segments: outside [n, {cap}]")
+        work = torch.empty(5 * cap, dtype=torch.int32, device=self.device)
+        count = torch.empty(1, dtype=torch.int32, device=self.device)          # written, never read
+        _lib.check(lib.hsg_rel_work(n, _lib.ptr(indptr), pmin, mult, _lib.ptr(work), cap, _lib.ptr(count), st),
+                   "hsg_rel_work")
+        return work[:5 * items]
+
+    def batch(self, indices, model_view=None, doc_view=None):
         """``(G, index)`` as ``graph_collate_fn`` gives them for the same documents: sorted by
         sentence count (descending, ties in the order given), ``G`` on the device.
 
@@ -455,8 +589,16 @@ class DocumentStore:
         the batch carries the model's index structures (``G.model_inputs`` and the entries the
         model caches on the graph), assembled by one more launch.  A store that declined the
         view at build (``store.model_view`` False, ``store.model_view_reason``) never attaches
-        it.  False is the batch without it, bit for bit."""
+        it.  False is the batch without it, bit for bit.
+
+        ``doc_view``: None (:attr:`DOC_VIEW`), True or False -- whether a batch with the model
+        view also carries HSumDocGraph's doc-side layouts (the entries ``HiGraph._hdsg_layout``
+        and ``_hdsg_head_layout`` cache on the graph), assembled by one more launch, and has its
+        work lists sized on the host instead of read back.  A store that declined it
+        (``store.doc_view`` False, ``store.doc_view_reason``) never attaches it.  False is
+        today's batch, bit for bit, read-back included."""
         view = self.model_view and (self.MODEL_VIEW if model_view is None else bool(model_view))
+        dview = view and self.doc_view and (self.DOC_VIEW if doc_view is None else bool(doc_view))
         slots = self.slots_of(indices)
         B = len(slots)
         if B < 1:
@@ -481,9 +623,22 @@ class DocumentStore:
                 if not lib.hsg_res_model_supported(B, n_s, E, int(rowbase[B])):
                     raise RuntimeError(f"batch of {B} documents, {n_s} sentences, {int(rowbase[B])} token rows: "
                                        "beyond hsg_res_model_supported")
-                both = torch.from_numpy(np.concatenate([slots, rowbase]).astype(np.int32))
+                host = [slots, rowbase]
+                if dview:
+                    # the doc-node and pair running offsets ride in the same copy
+                    docbase, pairbase = np.zeros(B + 1, np.int64), np.zeros(B + 1, np.int64)
+                    np.cumsum(self.docn[slots], out=docbase[1:])
+                    np.cumsum(self.pairs[slots], out=pairbase[1:])
+                    n_dn, n_pr, n_su = int(docbase[B]), int(pairbase[B]), int(tot[DST(0)])
+                    if not lib.hsg_res_hdsg_supported(B, n_s, n_dn, n_pr, n_su):
+                        raise RuntimeError(f"batch of {B} documents, {n_dn} doc nodes, {n_pr} sentence-doc pairs: "
+                                           "beyond hsg_res_hdsg_supported")
+                    host += [docbase, pairbase]
+                both = torch.from_numpy(np.concatenate(host).astype(np.int32))
                 both = both.pin_memory().to(dev, non_blocking=True)
-                pick, rowbase_d = both[:B], both[B:]
+                pick, rowbase_d = both[:B], both[B:2 * B + 1]
+                if dview:
+                    docbase_d, pairbase_d = both[2 * B + 1:3 * B + 2], both[3 * B + 2:]
             else:
                 pick = torch.from_numpy(slots.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
             offs = new(NFAM * (B + 1), i64)
@@ -520,7 +675,13 @@ class DocumentStore:
                 lng = self.longest[slots, q].max(0)
                 need = needs_work_list(ndst, nt, int(lng[0])) or needs_work_list(ns, nt, int(lng[1]))
                 G.resident_work_lists[kind] = need
-                if need:
+                if need and dview and int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN))) >= PIECE_MIN:
+                    # each side's item count from the kept segment lengths: no read-back
+                    for key, side, cnt, ptr_key in (("dwork", 0, ndst, "indptr"), ("swork", 1, ns, "cindptr")):
+                        items = work_items(cnt, nt, self._long(q, side, slots))
+                        if items > 0:
+                            d[key] = self._sized_work_list(lib, cnt, d[ptr_key], nt, items, st)
+                elif need:
                     attach_work_lists(d, ns, ndst, nt)         # today's path, with its read-back
                 G._rel_cache[("rel", kind, str(dev))] = Relation.on_device(kind, ns, ndst, d, E)
             if view:
@@ -536,6 +697,20 @@ class DocumentStore:
                 words = G._rel_cache[("rel", "W2S", str(dev))].dev["src_nodes"]
                 for key, val in zip(VIEW_KEYS, (words, t["sent_nodes"], glen, t["tfidf_index"], t["doc_off"])):
                     G._rel_cache[(key, str(dev))] = val
+            if dview:
+                from .head import HeadLayout
+                sizes = dict(pair_s=n_pr, pair_d=n_pr, super_pos=n_su, sent_super=n_s, doc_super=n_s, super_src=n_su,
+                             doc_ptr=n_dn + 1, doc_sent=n_pr, sent_ptr=n_s + 1, sent_doc=n_pr, sent_row=n_s,
+                             doc_row=n_dn, sup_sent=n_su, sup_ptr=n_su + 1, sup_list=n_s)
+                lay = {k: new(sizes[k], i64) for k in HDSG_DICT}
+                inv_cnt = new(n_dn, f32)
+                lists = {k: new(sizes[k], i32) for k in HDSG_HEAD}
+                _lib.check(lib.hsg_res_hdsg(cs, ctypes.byref(self._hdsg_cstruct), B, p(pick), p(offs), p(docbase_d),
+                                            p(pairbase_d), n_s, n_dn, n_pr, n_su, *[p(v) for v in lay.values()],
+                                            p(inv_cnt), *[p(v) for v in lists.values()], st), "hsg_res_hdsg")
+                # under the keys HiGraph._hdsg_layout / _hdsg_head_layout use
+                G._rel_cache[(HDSG_KEYS[0], str(dev))] = dict(lay, inv_cnt=inv_cnt, n_docs=n_dn)
+                G._rel_cache[(HDSG_KEYS[1], str(dev))] = HeadLayout.prebuilt(n_s, n_dn, n_su, inv_cnt, **lists)
             # the launches above read pick and offs after this returns: the allocator keeps a
             # freed block for later work of the SAME stream, so dropping them here is safe
         if self.eval_words is not None:
@@ -546,13 +721,15 @@ class DocumentStore:
 class ResidentLoader:
     """Iterates ``(G, index)`` like ``DataLoader(dataset, batch_size, shuffle, collate_fn=
     graph_collate_fn)``, from a :class:`DocumentStore`.  The permutation is drawn on the host
-    from ``generator``; ``index`` holds dataset indices; ``model_view`` is :meth:`DocumentStore.batch`'s."""
+    from ``generator``; ``index`` holds dataset indices; ``model_view`` and ``doc_view`` are
+    :meth:`DocumentStore.batch`'s."""
 
-    def __init__(self, store, batch_size, shuffle=False, generator=None, drop_last=False, model_view=None):
+    def __init__(self, store, batch_size, shuffle=False, generator=None, drop_last=False, model_view=None,
+                 doc_view=None):
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
         self.store, self.batch_size, self.shuffle = store, int(batch_size), shuffle
-        self.generator, self.drop_last, self.model_view = generator, drop_last, model_view
+        self.generator, self.drop_last, self.model_view, self.doc_view = generator, drop_last, model_view, doc_view
 
     def __len__(self):
         n = len(self.store)
@@ -570,5 +747,7 @@ class ResidentLoader:
 
     def __iter__(self):
         kw = {} if self.model_view is None else {"model_view": self.model_view}     # None: the store's default
+        if self.doc_view is not None:
+            kw["doc_view"] = self.doc_view
         for idx in self.batches():
             yield self.store.batch(idx, **kw)
