@@ -36,6 +36,12 @@ device splits them at ``str.split()``'s whitespace and interns the words
 (``hsg_eval_text_words``, include/hsg_eval_text.h), and the unchanged ``hsg_eval_select_words``
 selects.  Ids attached to the graph are used as they are; the per-example cache is neither
 read nor filled.
+
+In both of these modes a resident batch that carries the eval view (``G.eval_pack``,
+``resident.DocumentStore.batch``, include/hsg_resident_eval.h) brings its word pack along, already
+on the device: nothing is packed, pinned or uploaded here, the seen set is sized from the
+store's cache, and the batch's examples are read from the dataset in ``_drain``, behind the
+launches.
 """
 from __future__ import annotations
 
@@ -213,10 +219,16 @@ class SLTester(TestPipLine):
         dev = outputs.device
         counts = sentence_counts(G)
         B = len(counts)
+        # a resident batch with the eval view carries its word pack, assembled on the device
+        # (resident.DocumentStore.batch, G.eval_pack): nothing is packed or uploaded here, and
+        # the dataset is first read in _drain, behind the launches
+        view = getattr(G, "eval_pack", None) if blocking and self.m != 0 and mode in ("words", "text") else None
         # host work while the forward runs: the examples and the blocking operands
-        examples = [dataset.get_example(index[j]) for j in range(B)]
+        examples = None if view is not None else [dataset.get_example(index[j]) for j in range(B)]
         pack = text = None
-        if blocking and self.m != 0 and mode in ("words", "text"):
+        if view is not None:
+            pack = view
+        elif blocking and self.m != 0 and mode in ("words", "text"):
             # word ids: from the graph if the dataset attached them; else made once per example
             # ("words"), or made on the device from the sentences' bytes ("text")
             parts = getattr(G, "eval_words", None)
@@ -256,13 +268,16 @@ class SLTester(TestPipLine):
         host.copy_(out[:B * (sel_ld + 1)], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        prev, self._pending = self._pending, (ev, host, sel_ld, counts, examples, mode)
+        source = None if examples is not None else (dataset, [index[j] for j in range(B)])
+        prev, self._pending = self._pending, (ev, host, sel_ld, counts, examples, mode, source)
         if prev is not None:
             self._drain(prev)
 
     def _drain(self, pending):
         """The host half of one batch (Tester.py:138-143), once its indices have arrived."""
-        ev, host, sel_ld, counts, examples, mode = pending
+        ev, host, sel_ld, counts, examples, mode, source = pending
+        if examples is None:                 # an eval-view batch: its examples are read here
+            examples = [source[0].get_example(i) for i in source[1]]
         ev.synchronize()
         B = len(counts)
         sel = host[:B * sel_ld].view(B, sel_ld).tolist()

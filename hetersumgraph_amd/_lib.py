@@ -78,6 +78,12 @@ class HsgResHdsgCols(ctypes.Structure):
                                                "inv_cnt", "doc_ptr", "doc_row", "sup_code", "sup_sent", "sup_ptr")]
 
 
+class HsgResEvalCols(ctypes.Structure):
+    """Mirror of ``struct hsg_res_eval_cols`` (include/hsg_resident_eval.h)."""
+
+    _fields_ = [(k, ctypes.c_void_p) for k in ("wstart", "wend", "wid")]
+
+
 # count families of the resident store (include/hsg_resident.h); q = 0 (W2S), 1 (S2W)
 HSG_RES_NODE, HSG_RES_EDGE, HSG_RES_SENT, HSG_RES_NFAM = 0, 1, 2, 9
 HSG_RES_SRC = lambda q: 3 + 3 * q
@@ -254,6 +260,11 @@ ABI["hsg_resident_hdsg.h"] = {
     "hsg_res_hdsg_supported": [_I, _L64, _L64, _L64, _L64],
     # cols (const hsg_res_hdsg_cols *) is bound as a plain pointer: pass ctypes.byref(HsgResHdsgCols)
     "hsg_res_hdsg": [_RESP, _P, _I, _P, _P, _P, _P, _L64, _L64, _L64, _L64] + [_P] * 19,
+}
+ABI["hsg_resident_eval.h"] = {
+    "hsg_res_eval_supported": [_I, _L64, _L64],
+    # cols (const hsg_res_eval_cols *) is bound as a plain pointer: pass ctypes.byref(HsgResEvalCols)
+    "hsg_res_eval": [_RESP, _P, _I, _P, _P, _P, _L64, _L64, _P, _P],
 }
 ABI["hsg_cnn_tokens.h"] = {
     "hsg_cnn_tok_supported": [_I, _I],

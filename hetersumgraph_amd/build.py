@@ -20,7 +20,7 @@ ROOT = os.path.dirname(HERE)
 SOURCES = [os.path.join(HERE, "csrc", f) for f in ("hsg_gat.hip", "hsg_attn.hip", "hsg_gemm.hip", "hsg_rows.hip", "hsg_hproj.hip", "hsg_relbuild.hip", "hsg_cnn.hip", "hsg_ffn.hip", "hsg_dw.hip",
                                                      "hsg_lstm.hip", "hsg_train.hip", "hsg_model.hip", "hsg_embed.hip", "hsg_eval.hip",
                                                      "hsg_eval_text.hip", "hsg_resident.hip", "hsg_resident_model.hip",
-                                                     "hsg_resident_hdsg.hip",
+                                                     "hsg_resident_hdsg.hip", "hsg_resident_eval.hip",
                                                      "hsg_cnn_tokens.hip",
                                                      "hsg_lstm_train.hip")]
 OUT = os.path.join(HERE, "libhsg.so")

@@ -30,6 +30,13 @@ launch; and it keeps the lengths of every segment longer than ``relation.PIECE_M
 the item count of a batch's work lists follows on the host (:func:`work_items`), so
 ``hsg_rel_work`` runs without its read-back.  ``doc_view=False`` is the batch without both.
 
+A store that was handed the documents' word ids (``eval_words``) keeps them on the device in
+local form and hands the evaluation step its blocking operand with the batch (the *eval view*,
+include/hsg_resident_eval.h: ``G.eval_pack``, bit-equal to ``evalsel.pack_words(G.eval_words,
+counts)``, assembled by one launch), with the seen set sized from a per-store cache
+(:meth:`DocumentStore.seen_need`).  It is independent of the other two views;
+``eval_view=False`` is the batch without it.
+
 There is no fallback: a CPU device, a pick outside the store or a batch beyond
 ``hsg_res_supported`` raises.  Changing a dataset after its store was built is the caller's
 business (the store does not look at the dataset again).
@@ -42,6 +49,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .evalsel import WordPack
 from .graph import BatchedDGLGraph, Frame
 from .relation import HOT_KINDS, KINDS, Relation, attach_work_lists, build_relation
 from .relation import PIECE_MIN, PIECE_MULT
@@ -175,6 +183,57 @@ def doc_view_local(doc, no):
     return None, cols
 
 
+def eval_view_local(entry, n_sent):
+    """The local columns of one document's ``eval_words`` entry for its ``n_sent`` sentence rows
+    (include/hsg_resident_eval.h) -- ``dict(wend=ptr[1:] int32, wid=ids int32, lens=words per
+    row int64)`` -- or, as a ``str``, why the entry cannot carry the eval view.  Accepted: a list
+    of exactly one ``(ptr, ids)`` pair of ``evalsel.word_ids``' form: integral 1-D arrays,
+    ``len(ptr) == n_sent + 1``, ``ptr[0] == 0``, ``ptr`` non-decreasing, ``ptr[-1] == len(ids)``,
+    ids that fit int32."""
+    if not isinstance(entry, (list, tuple)):
+        return f"its eval_words entry is a {type(entry).__name__}, not a list of one (ptr, ids) pair"
+    if len(entry) != 1:
+        return f"its eval_words entry has {len(entry)} parts, not one (ptr, ids) pair"
+    pair = entry[0]
+    if not isinstance(pair, (list, tuple)) or len(pair) != 2:
+        return "its eval_words part is not a (ptr, ids) pair"
+    ptr_, ids = np.asarray(pair[0]), np.asarray(pair[1])
+    if ptr_.ndim != 1 or ids.ndim != 1 or ptr_.dtype.kind not in "iu" or (ids.size and ids.dtype.kind not in "iu"):
+        return "its (ptr, ids) are not one-dimensional integer arrays"
+    if len(ptr_) != int(n_sent) + 1:
+        return f"its word ptr has {len(ptr_)} elements for {int(n_sent)} sentence rows (rows + 1 expected)"
+    ptr_ = ptr_.astype(np.int64)
+    if ptr_[0] != 0:
+        return f"its word ptr begins at {int(ptr_[0])}, not 0"
+    lens = np.diff(ptr_)
+    if (lens < 0).any():
+        return "its word ptr decreases"
+    if ptr_[-1] != len(ids):
+        return f"its word ptr ends at {int(ptr_[-1])} for {len(ids)} word ids"
+    if ids.size and (int(ids.min()) < -I32_MAX - 1 or int(ids.max()) > I32_MAX):
+        return "a word id does not fit int32"
+    return dict(wend=ptr_[1:].astype(np.int32), wid=ids.astype(np.int32), lens=lens)
+
+
+def seen_columns(lens):
+    """``(lens_desc, doc_of_row, rank)`` of :func:`seen_need` from every document's words per
+    row (a list of int arrays, one per document)."""
+    n_rows = np.asarray([len(a) for a in lens], np.int64)
+    lens_desc = np.concatenate([-np.sort(-np.asarray(a, np.int64)) for a in lens] or [np.zeros(0, np.int64)])
+    doc_of_row = np.repeat(np.arange(len(lens)), n_rows)
+    rank = np.arange(len(doc_of_row)) - np.repeat(np.cumsum(n_rows) - n_rows, n_rows)
+    return lens_desc, doc_of_row, rank
+
+
+def seen_need(lens_desc, doc_of_row, rank, n_docs, n_win, m):
+    """Per document, ``evalsel.WordPack.win_need``'s term: the sum of the ``min(m, N_d)`` largest
+    per-row window counts ``max(len - n_win, 0)``.  ``lens_desc``: every document's words per row,
+    each document's sorted descending (subtracting ``n_win`` keeps that order); ``doc_of_row`` and
+    ``rank``: the row's document and its position inside it.  int64 ``[n_docs]``."""
+    win = np.maximum(lens_desc - int(n_win), 0) * (rank < int(m))
+    return np.bincount(doc_of_row, weights=win, minlength=n_docs).astype(np.int64)
+
+
 def sentence_layout(words):
     """Host statement of ``cnn._layout`` for one document's token rows [N, L]: (length [N],
     the exclusive prefix of ``length + 1`` [N], the row count, whether a non-zero token follows
@@ -226,6 +285,26 @@ class ModelInputs:
             from .lstm import DocLayout
             self._lstm = DocLayout.prebuilt(self.glen, self.doc_off, self.prev)
         return self._lstm
+
+
+class ResidentWordPack(WordPack):
+    """The eval view of one resident batch (include/hsg_resident_eval.h): an
+    ``evalsel.WordPack`` whose buffer was assembled on the device -- bit-equal to
+    ``pack_words(G.eval_words, counts).buf`` -- and whose :meth:`win_need` (so ``tab_cap``) is one
+    ``max`` over the store's cached per-document values instead of a sort per document."""
+
+    def __init__(self, buf, n, B, W, counts, store, slots):
+        super().__init__(buf, n, B, W, None, counts)
+        self._store, self._slots = store, slots
+
+    def to(self, device):
+        if _device(device, allow_cpu=True) == self.buf.device:
+            return self
+        return ResidentWordPack(self.buf.to(device, non_blocking=True), self.n, self.B, self.W, self.counts,
+                                self._store, self._slots)
+
+    def win_need(self, n_win, m):
+        return int(self._store.seen_need(n_win, m)[self._slots].max(initial=0))
 
 
 class ResidentBatch(BatchedDGLGraph):
@@ -344,6 +423,7 @@ class DocumentStore:
 
     MODEL_VIEW = True                 # batch()'s default for ``model_view`` (measured: DESIGN.md §6)
     DOC_VIEW = True                   # batch()'s default for ``doc_view`` (measured: DESIGN.md §6)
+    EVAL_VIEW = True                  # batch()'s default for ``eval_view`` (measured: DESIGN.md §6)
 
     # ------------------------------------------------------------------ build
     def __init__(self, device):
@@ -356,6 +436,7 @@ class DocumentStore:
         (default: its position); ``eval_words``: per document, what ``G.eval_words`` of its
         one-member batch holds (``ExampleSet(eval_words=True)``)."""
         docs = list(docs)
+        eval_words = None if eval_words is None else list(eval_words)
         return cls._build([docs[i:i + chunk] for i in range(0, len(docs), max(1, int(chunk)))], device, indices,
                           eval_words)
 
@@ -397,6 +478,11 @@ class DocumentStore:
         self.doc_view, self.doc_view_reason = True, None
         hdsg = {k: [] for fam in HDSG_COLUMNS.values() for k in fam}
         long_lens = [[[], []] for _ in HOT_KINDS]
+        # the eval view (include/hsg_resident_eval.h): per document the local (ptr, ids) of its
+        # eval_words entry; an entry of another form makes the store decline the view
+        self.eval_view = eval_words is not None
+        self.eval_view_reason = None if self.eval_view else "the store was built without eval_words"
+        ev = {k: [] for k in ("wend", "wid", "lens")}
         n_seen = 0
         for docs in chunks:
             if not docs:
@@ -456,6 +542,13 @@ class DocumentStore:
                     self.doc_view = self.doc_view_reason is None
                     for k, a in (local or {}).items():
                         hdsg[k].append(a)
+                if self.eval_view:
+                    ew = eval_view_local(eval_words[no], N) if no < len(eval_words) else "it has no eval_words entry"
+                    if isinstance(ew, str):
+                        self.eval_view, self.eval_view_reason = False, f"document {no}: {ew}"
+                    else:
+                        for k, a in ew.items():
+                            ev[k].append(a)
                 for q, sides in enumerate(long_segments(doc)):
                     for side, lens in enumerate(sides):
                         long_lens[q][side].append(lens)
@@ -510,6 +603,19 @@ class DocumentStore:
                                for k, v in hdsg.items()}
             self._hdsg_cols.update(dstart=starts(self.docn), pstart=starts(self.pairs))
             self._hdsg_cstruct = _lib.HsgResHdsgCols(**{k: _lib.ptr(v) for k, v in self._hdsg_cols.items()})
+        self._eval_cols, self._eval_cstruct, self._need = {}, None, {}
+        if self.eval_view:
+            self.words_of = np.asarray([len(a) for a in ev["wid"]], np.int64)       # [n_docs] words
+            wstart = np.concatenate([[0], np.cumsum(self.words_of)]).astype(np.int64)
+            flat = lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dt)
+            self._eval_cols = {k: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                               for k, a in (("wstart", wstart), ("wend", flat(ev["wend"], np.int32)),
+                                            ("wid", flat(ev["wid"], np.int32)))}
+            self._eval_cstruct = _lib.HsgResEvalCols(**{k: _lib.ptr(v) if v.numel() else None
+                                                        for k, v in self._eval_cols.items()})
+            # what sizes the seen set: every document's words per row sorted descending, each
+            # row's document and its position inside it (seen_need)
+            self._lens_desc, self._row_doc, self._row_rank = seen_columns(ev["lens"])
         self._starts_d = torch.from_numpy(self.starts).to(dev)
         self._bases_d = torch.from_numpy(self.bases).to(dev)
         p = _lib.ptr
@@ -526,7 +632,18 @@ class DocumentStore:
 
     def _tensors(self):
         return list(self._cols.values()) + list(self._view_cols.values()) + list(self._hdsg_cols.values()) + \
-            [t for r in self._rels for t in r.values()] + [self._starts_d, self._bases_d]
+            list(self._eval_cols.values()) + [t for r in self._rels for t in r.values()] + \
+            [self._starts_d, self._bases_d]
+
+    def seen_need(self, n_win, m):
+        """Per document of the store, :func:`seen_need` for windows of ``n_win`` words and ``m``
+        chosen sentences: int64 ``[n_docs]``, computed once per pair and kept."""
+        key = (int(n_win), int(m))
+        if key not in self._need:
+            if not self.eval_view:
+                raise RuntimeError("the store declined the eval view: " + self.eval_view_reason)
+            self._need[key] = seen_need(self._lens_desc, self._row_doc, self._row_rank, self._docs, *key)
+        return self._need[key]
 
     @property
     def nbytes(self):
@@ -581,7 +698,7 @@ class DocumentStore:
                    "hsg_rel_work")
         return work[:5 * items]
 
-    def batch(self, indices, model_view=None, doc_view=None):
+    def batch(self, indices, model_view=None, doc_view=None, eval_view=None):
         """``(G, index)`` as ``graph_collate_fn`` gives them for the same documents: sorted by
         sentence count (descending, ties in the order given), ``G`` on the device.
 
@@ -596,9 +713,19 @@ class DocumentStore:
         and ``_hdsg_head_layout`` cache on the graph), assembled by one more launch, and has its
         work lists sized on the host instead of read back.  A store that declined it
         (``store.doc_view`` False, ``store.doc_view_reason``) never attaches it.  False is
-        today's batch, bit for bit, read-back included."""
+        today's batch, bit for bit, read-back included.
+
+        ``eval_view``: None (:attr:`EVAL_VIEW`), True or False -- whether the batch carries the
+        evaluation step's word pack (``G.eval_pack``, an ``evalsel.WordPack`` on the device that
+        is bit-equal to ``pack_words(G.eval_words, counts)`` and sizes the seen set from the
+        store's cache), assembled by one more launch; independent of the other two views.  A
+        store built without ``eval_words``, or with entries of another form than one
+        ``word_ids`` pair per document (``store.eval_view`` False, ``store.eval_view_reason``),
+        never attaches it.  False is today's batch, bit for bit; ``G.eval_words`` is attached
+        either way."""
         view = self.model_view and (self.MODEL_VIEW if model_view is None else bool(model_view))
         dview = view and self.doc_view and (self.DOC_VIEW if doc_view is None else bool(doc_view))
+        eview = self.eval_view and (self.EVAL_VIEW if eval_view is None else bool(eval_view))
         slots = self.slots_of(indices)
         B = len(slots)
         if B < 1:
@@ -612,6 +739,16 @@ class DocumentStore:
         new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         i32, i64, f32 = torch.int32, torch.int64, torch.float32
         L, M = self.sent_len, self.label_len
+        n_s = int(tot[SENT])
+        if eview:
+            # the word running offsets, summed on the host from the kept counts, ride in the
+            # pinned copy that carries the pick list
+            wordbase = np.zeros(B + 1, np.int64)
+            np.cumsum(self.words_of[slots], out=wordbase[1:])
+            n_w = int(wordbase[B])
+            if not lib.hsg_res_eval_supported(B, n_s, n_w):
+                raise RuntimeError(f"batch of {B} documents, {n_s} sentences, {n_w} words: beyond "
+                                   "hsg_res_eval_supported")
         with torch.cuda.device(dev):
             # one small pinned copy, not waited for (the pinned block is recycled stream-safely)
             if view:
@@ -619,7 +756,6 @@ class DocumentStore:
                 # behind the pick list in the same pinned copy
                 rowbase = np.zeros(B + 1, np.int64)
                 np.cumsum(self.rows_of[slots], out=rowbase[1:])
-                n_s = int(tot[SENT])
                 if not lib.hsg_res_model_supported(B, n_s, E, int(rowbase[B])):
                     raise RuntimeError(f"batch of {B} documents, {n_s} sentences, {int(rowbase[B])} token rows: "
                                        "beyond hsg_res_model_supported")
@@ -634,11 +770,19 @@ class DocumentStore:
                         raise RuntimeError(f"batch of {B} documents, {n_dn} doc nodes, {n_pr} sentence-doc pairs: "
                                            "beyond hsg_res_hdsg_supported")
                     host += [docbase, pairbase]
+                if eview:
+                    host.append(wordbase)
                 both = torch.from_numpy(np.concatenate(host).astype(np.int32))
                 both = both.pin_memory().to(dev, non_blocking=True)
                 pick, rowbase_d = both[:B], both[B:2 * B + 1]
                 if dview:
-                    docbase_d, pairbase_d = both[2 * B + 1:3 * B + 2], both[3 * B + 2:]
+                    docbase_d, pairbase_d = both[2 * B + 1:3 * B + 2], both[3 * B + 2:4 * B + 3]
+                if eview:
+                    wordbase_d = both[len(both) - (B + 1):]
+            elif eview:
+                both = torch.from_numpy(np.concatenate([slots, wordbase]).astype(np.int32))
+                both = both.pin_memory().to(dev, non_blocking=True)
+                pick, wordbase_d = both[:B], both[B:]
             else:
                 pick = torch.from_numpy(slots.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
             offs = new(NFAM * (B + 1), i64)
@@ -711,6 +855,12 @@ class DocumentStore:
                 # under the keys HiGraph._hdsg_layout / _hdsg_head_layout use
                 G._rel_cache[(HDSG_KEYS[0], str(dev))] = dict(lay, inv_cnt=inv_cnt, n_docs=n_dn)
                 G._rel_cache[(HDSG_KEYS[1], str(dev))] = HeadLayout.prebuilt(n_s, n_dn, n_su, inv_cnt, **lists)
+            if eview:
+                pack = new(n_s + 1 + max(n_w, 1), i32)
+                _lib.check(lib.hsg_res_eval(cs, ctypes.byref(self._eval_cstruct), B, p(pick), p(offs), p(wordbase_d),
+                                            n_s, n_w, p(pack), st), "hsg_res_eval")
+                G.eval_pack = ResidentWordPack(pack, n_s, B, n_w, [int(x) for x in self.counts[slots, SENT]], self,
+                                               slots)
             # the launches above read pick and offs after this returns: the allocator keeps a
             # freed block for later work of the SAME stream, so dropping them here is safe
         if self.eval_words is not None:
@@ -721,15 +871,16 @@ class DocumentStore:
 class ResidentLoader:
     """Iterates ``(G, index)`` like ``DataLoader(dataset, batch_size, shuffle, collate_fn=
     graph_collate_fn)``, from a :class:`DocumentStore`.  The permutation is drawn on the host
-    from ``generator``; ``index`` holds dataset indices; ``model_view`` and ``doc_view`` are
-    :meth:`DocumentStore.batch`'s."""
+    from ``generator``; ``index`` holds dataset indices; ``model_view``, ``doc_view`` and
+    ``eval_view`` are :meth:`DocumentStore.batch`'s."""
 
     def __init__(self, store, batch_size, shuffle=False, generator=None, drop_last=False, model_view=None,
-                 doc_view=None):
+                 doc_view=None, eval_view=None):
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
         self.store, self.batch_size, self.shuffle = store, int(batch_size), shuffle
         self.generator, self.drop_last, self.model_view, self.doc_view = generator, drop_last, model_view, doc_view
+        self.eval_view = eval_view
 
     def __len__(self):
         n = len(self.store)
@@ -749,5 +900,7 @@ class ResidentLoader:
         kw = {} if self.model_view is None else {"model_view": self.model_view}     # None: the store's default
         if self.doc_view is not None:
             kw["doc_view"] = self.doc_view
+        if self.eval_view is not None:
+            kw["eval_view"] = self.eval_view
         for idx in self.batches():
             yield self.store.batch(idx, **kw)
