@@ -275,6 +275,10 @@ ABI["hsg_cnn_tokens.h"] = {
     "hsg_cnn_tok_dw_ws_floats": [_I, _I],
     "hsg_cnn_tok_dw": [_I, _I, _I, _I] + [_P] * 8 + [_P, _I, _P, _P],
 }
+ABI["hsg_cnn_vocab.h"] = {
+    "hsg_cnn_vocab_supported": [_I],
+    "hsg_cnn_vocab_pool": [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+}
 ABI["hsg_lstm_train.h"] = {
     "hsg_lstm_train_supported": [_I, _I, _I],
     "hsg_lstm_pack_layer_offset": [_I, _I, _I, _I],

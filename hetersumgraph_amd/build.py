@@ -21,7 +21,7 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in ("hsg_gat.hip", "hsg_attn.hip"
                                                      "hsg_lstm.hip", "hsg_train.hip", "hsg_model.hip", "hsg_embed.hip", "hsg_eval.hip",
                                                      "hsg_eval_text.hip", "hsg_resident.hip", "hsg_resident_model.hip",
                                                      "hsg_resident_hdsg.hip", "hsg_resident_eval.hip",
-                                                     "hsg_cnn_tokens.hip",
+                                                     "hsg_cnn_tokens.hip", "hsg_cnn_vocab.hip",
                                                      "hsg_lstm_train.hip")]
 OUT = os.path.join(HERE, "libhsg.so")
 OBJDIR = os.path.join(ROOT, "build", "obj")
@@ -63,7 +63,9 @@ def _flags(dev=False):
 FILE_FLAGS = {"hsg_hproj.hip": ["-fno-slp-vectorize"],
               # the token paths' order contracts are written in separately rounded multiplies and
               # adds (include/hsg_cnn_tokens.h): no a * b + c -> fma anywhere in the file
-              "hsg_cnn_tokens.hip": ["-ffp-contract=off"]}
+              "hsg_cnn_tokens.hip": ["-ffp-contract=off"],
+              # the same value contract, restated on the vocabulary table (include/hsg_cnn_vocab.h)
+              "hsg_cnn_vocab.hip": ["-ffp-contract=off"]}
 
 
 def _obj(src, dev=False):

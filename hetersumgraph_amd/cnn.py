@@ -313,6 +313,123 @@ def sent_cnn_switched(ids, embed_weight, pos_weight, conv_weights, conv_biases, 
     return sent_cnn(ids, embed_weight, pos_weight, conv_weights, conv_biases, padding_idx=padding_idx, layout=layout)
 
 
+# ---------------------------------------------------------------------------------------------
+# Opt-in (``path_options(HSG_SENT_CNN_VOCAB="1")``, include/hsg_cnn_vocab.h), for a forward that
+# records no gradient (model.eval() under torch.no_grad()): the identity of the "tokens" path with
+# the products taken over the WHOLE vocabulary, once per evaluation pass.  TW = [E ; P] Wall^T is
+# a constant while no parameter changes, so a batch's forward is one launch that gathers TW rows
+# by token id: no mark, scan, table copy, GEMM or read-back per batch.
+VOCAB_SWITCH = "HSG_SENT_CNN_VOCAB"
+VOCAB_BUDGET = "HSG_SENT_CNN_VOCAB_MB"        # the largest table built, MiB; 1024 covers vocab_size = 50000
+
+
+def sent_cnn_vocab_on():
+    """The value of the ``HSG_SENT_CNN_VOCAB`` switch as a bool ("0" or "1"); anything else raises."""
+    v = _lib.path_option(VOCAB_SWITCH, "0")
+    if v not in ("0", "1"):
+        raise ValueError(f"{VOCAB_SWITCH}={v!r}: one of 0, 1")
+    return v == "1"
+
+
+def vocab_table_bytes(V, Pn):
+    return (V + Pn) * LDY * 4
+
+
+def vocab_path_ok(ids, embed_weight, pos_weight, conv_weights, conv_biases) -> bool:
+    """The vocabulary path covers this call: :func:`token_path_ok`'s conditions on device, dtype,
+    contiguity, shape and HSG_CHECK_NAN, without the frozen-table one; no gradient will be recorded
+    (grad mode off, or no parameter of the encoder requires grad); and the table over the whole
+    vocabulary fits ``HSG_SENT_CNN_VOCAB_MB`` (a path option, default 1024)."""
+    from .module.GATLayer import CHECK_NAN
+    conv_weights, conv_biases = list(conv_weights), list(conv_biases)
+    floats = [embed_weight, pos_weight] + conv_weights + conv_biases
+    if CHECK_NAN or len(conv_weights) != len(HEIGHTS) or len(conv_biases) != len(HEIGHTS):
+        return False
+    if not ids.is_cuda or ids.dim() != 2 or any(not t.is_cuda or t.dtype != torch.float32 for t in floats):
+        return False
+    if torch.is_grad_enabled() and any(t.requires_grad for t in floats):
+        return False
+    if embed_weight.dim() != 2 or pos_weight.dim() != 2 or not embed_weight.is_contiguous() \
+            or not pos_weight.is_contiguous():
+        return False
+    L, (V, D) = ids.shape[1], embed_weight.shape
+    if pos_weight.shape[1] != D or D % 4 or D < 4 or V < 1 or L > pos_weight.shape[0] - 1:
+        return False
+    for h, w, b in zip(HEIGHTS, conv_weights, conv_biases):
+        if tuple(w.shape) != (CHANNELS, 1, h, D) or tuple(b.shape) != (CHANNELS,):
+            return False
+    budget = float(_lib.path_option(VOCAB_BUDGET, "1024")) * (1 << 20)
+    if vocab_table_bytes(V, pos_weight.shape[0]) > budget:
+        return False
+    return bool(load().hsg_cnn_vocab_supported(L))
+
+
+class VocabTable:
+    """``TW [V + Pn, LDY]``: rows 0..V-1 = E Wall^T, rows V + p = P[p] Wall^T (two GEMMs), built on
+    first use and rebuilt when its key changes.  The key holds numbers only -- ``data_ptr()``,
+    ``_version``, shape and device of the embedding, the position table and the six conv weights,
+    and the GEMM mode -- so the table keeps no parameter alive.  A write that moves no version
+    counter (``.data``, a foreign kernel) is not seen: :meth:`drop` (``sentEncoder.train()`` /
+    ``.eval()`` call it)."""
+
+    def __init__(self):
+        self.drop()
+
+    def drop(self):
+        self.key = self.TW = None
+        self.V = 0
+        self.builds = getattr(self, "builds", 0)
+
+    @staticmethod
+    def key_of(embed_weight, pos_weight, conv_weights):
+        from .dense import get_gemm_dtype
+        return tuple((t.data_ptr(), t._version, tuple(t.shape), str(t.device))
+                     for t in [embed_weight, pos_weight] + list(conv_weights)) + (get_gemm_dtype(),)
+
+    def nbytes(self):
+        return 0 if self.TW is None else self.TW.numel() * 4
+
+    def get(self, embed_weight, pos_weight, conv_weights):
+        """This table, current for these parameters."""
+        key = self.key_of(embed_weight, pos_weight, conv_weights)
+        if key != self.key:
+            self.drop()                               # the old table is freed before the new one is made
+            with torch.no_grad():
+                V, Pn = embed_weight.shape[0], pos_weight.shape[0]
+                wall = stack_taps([w.detach().float() for w in conv_weights])
+                TW = embed_weight.new_empty(V + Pn, LDY)
+                gemm(embed_weight.detach(), wall, b_t=True, out=TW[:V, :NY])
+                gemm(pos_weight.detach(), wall, b_t=True, out=TW[V:, :NY])
+            self.key, self.TW, self.V = key, TW, V
+            self.builds += 1
+        return self
+
+
+def sent_cnn_vocab(ids, table, conv_biases, layout=None):
+    """:func:`sent_cnn`'s forward on a current :class:`VocabTable` (the caller has asked
+    :func:`vocab_path_ok`): one ``hsg_cnn_vocab_pool`` launch -> [n, 300], no autograd node.  The
+    row layout is path "0"'s: computed from ``ids`` (one read-back, with the range check of the
+    ids), or the resident ``layout`` with its host-side range check."""
+    if table.TW is None:
+        raise RuntimeError("sent_cnn_vocab: the table is not built (VocabTable.get)")
+    n, L = ids.shape
+    TW, V = table.TW, table.V
+    if n == 0:
+        return TW.new_zeros(0, len(HEIGHTS) * CHANNELS)
+    ids = ids.long().contiguous()
+    if layout is None:
+        _, rowoff, _, _, _, _ = _layout_tokens(ids, V, False)
+    else:
+        _, rowoff, _ = layout.check(ids, V)
+    feat = TW.new_empty(n, len(HEIGHTS) * CHANNELS)
+    arg = torch.empty(n, len(HEIGHTS) * CHANNELS, dtype=torch.int32, device=TW.device)
+    bias = [b.detach().contiguous() for b in conv_biases]
+    bptr = (ctypes.c_void_p * len(bias))(*[b.data_ptr() for b in bias])
+    check(load().hsg_cnn_vocab_pool(n, L, V, ptr(ids), ptr(rowoff), ptr(TW), TW.stride(0), bptr, ptr(feat), ptr(arg),
+                                    stream_of(TW)), "hsg_cnn_vocab_pool")
+    return feat
+
+
 class _SentCNNRows(torch.autograd.Function):
     """:class:`_SentCNN` behind its gather: the row matrix X is a differentiable input."""
 

@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.init as init
 
+from .. import cnn as _cnn
 from ..cnn import sent_cnn_mode, sent_cnn_rows, sent_cnn_switched, token_path_ok
 from .PositionEmbedding import get_sinusoid_encoding_table
 
@@ -34,6 +35,27 @@ class sentEncoder(nn.Module):
         self.convs = nn.ModuleList([nn.Conv2d(1, 50, kernel_size=(kh, width)) for kh in range(2, 8)])
         for conv in self.convs:
             init.xavier_normal_(conv.weight.data, gain=np.sqrt(6.0))
+        # the vocabulary product table of the inference path (HSG_SENT_CNN_VOCAB): not a parameter,
+        # not a buffer, never in a state_dict
+        self._vocab_table = _cnn.VocabTable()
+
+    def _vocab_args(self):
+        return (self.embed.weight, self.position_embedding.weight, [c.weight for c in self.convs],
+                [c.bias for c in self.convs])
+
+    def _takes_vocab_path(self, input):
+        return _cnn.sent_cnn_vocab_on() and not self.training and _cnn.vocab_path_ok(input, *self._vocab_args())
+
+    def drop_vocab_table(self):
+        """Forget the vocabulary product table: the next no-grad forward builds a fresh one.  For a
+        parameter write the table's key cannot see (``.data``, a foreign kernel) inside one
+        ``eval()`` span."""
+        self._vocab_table.drop()
+
+    def train(self, mode=True):
+        # every model.train() / model.eval() starts a fresh table
+        self._vocab_table.drop()
+        return super().train(mode)
 
     def forward(self, input, layout=None):
         # input: [n_sent, L] token ids, PAD = 0 (trailing) -> [n_sent, 300]
@@ -41,12 +63,20 @@ class sentEncoder(nn.Module):
         # embedding, the sparse weight gradient / the forward on the batch's distinct tokens.
         # ``layout``: the sentences' prebuilt row layout (cnn.BatchLayout) instead of the one
         # computed, and read back, from ``input``
+        # Opt-in (``path_options(HSG_SENT_CNN_VOCAB="1")``): in eval mode, when no gradient is
+        # recorded, one gather launch on the vocabulary product table
+        if self._takes_vocab_path(input):
+            emb, pos, cw, cb = self._vocab_args()
+            return _cnn.sent_cnn_vocab(input, self._vocab_table.get(emb, pos, cw), cb, layout=layout)
         return sent_cnn_switched(input, self.embed.weight, self.position_embedding.weight,
                                  [c.weight for c in self.convs], [c.bias for c in self.convs],
                                  padding_idx=getattr(self.embed, "padding_idx", None), layout=layout)
 
     def takes_token_path(self, input):
-        """True when :meth:`forward` would run ``input`` on a token path (``HSG_SENT_CNN``)."""
+        """True when :meth:`forward` would run ``input`` on a token path (``HSG_SENT_CNN``) or on
+        the vocabulary path (``HSG_SENT_CNN_VOCAB``): the encoder then reads the ids itself."""
+        if self._takes_vocab_path(input):
+            return True
         return sent_cnn_mode() != "0" and token_path_ok(input, self.embed.weight, self.position_embedding.weight)
 
     def forward_rows(self, X, layout, shape):

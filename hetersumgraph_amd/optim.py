@@ -91,6 +91,7 @@ class Adam(torch.optim.Optimizer):
         self._pushed = None
         self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=self._device)
         self._key = self._arr = self._partials = None
+        self._updated = []
         self._T = 0
         self.refresh()
 
@@ -161,6 +162,7 @@ class Adam(torch.optim.Optimizer):
         if self._partials is None or self._partials.numel() < nb:
             self._partials = torch.empty(max(nb, 1), dtype=torch.float32, device=self._device)
         self._arr, self._T, self._key = arr, len(entries), self._table_key(ps)
+        self._updated = ps
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -180,6 +182,9 @@ class Adam(torch.optim.Optimizer):
               "hsg_mt_sqnorm")
         check(lib.hsg_mt_adam(self._arr, self._T, self._partials.data_ptr(), self._hyper.data_ptr(), 0,
                               self.last_grad_norm.data_ptr(), st), "hsg_mt_adam")
+        # the kernels write through raw pointers: move the version counters as an in-place op would
+        # (host-only), so that anything keyed on them (cnn.VocabTable) sees the step
+        torch.autograd.graph.increment_version(self._updated)
         return loss
 
     # --- checkpoints in torch.optim.Adam's layout -------------------------------------
