@@ -23,6 +23,8 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _lib
+
 # tf-idf box rows: 0..9 = _TFembed rows (HiGraph.py:52); row 10 = "no tfidfembed
 # written" (zero-initialised edge column, e.g. a typed edge with dtype != 0).
 N_BOX = 10
@@ -113,18 +115,30 @@ PIECE_MIN = 32
 PIECE_MULT = 1
 
 
-def _work_list(lib, n, indptr, n_edges, stream):
+def piece_params():
+    """``(pmin, mult)``: :data:`PIECE_MIN` and :data:`PIECE_MULT`, or what the path options
+    put in their place (dev A/B; ``pmin`` 0: no lists)."""
+    return (int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN))),
+            int(_lib.path_option("HSG_PIECE_MULT", str(PIECE_MULT))))
+
+
+def work_list_capacity(n, n_edges, pmin):
+    """The most items ``hsg_rel_work`` places for ``n`` segments over ``n_edges`` edges."""
+    return n + 2 * n_edges // pmin + 1
+
+
+def _work_list(lib, n, indptr, n_edges, stream, read_back=True, pieces=None):
     """(work: flat int32 [5 * cap] -- items of 4 int32, then the arrival counters -- or
     None) of one CSR / CSC: launched here, its item count read back by the caller
-    (``count``)."""
-    from . import _lib
-    pmin = int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN)))      # dev A/B (0: no lists)
-    mult = int(_lib.path_option("HSG_PIECE_MULT", str(PIECE_MULT)))
+    (``count``).  ``read_back=False``: the caller knows the count, so ``count`` is left
+    unfilled (the kernel writes it, nothing reads it).  ``pieces``: :func:`piece_params`' result,
+    where the caller has it."""
+    pmin, mult = pieces or piece_params()
     if n <= 0 or pmin <= 0:
         return None, None
-    cap = n + 2 * n_edges // pmin + 1
+    cap = work_list_capacity(n, n_edges, pmin)
     work = torch.empty(5 * cap, dtype=torch.int32, device=indptr.device)     # items (4 int32) + counters
-    count = torch.zeros(1, dtype=torch.int32, device=indptr.device)
+    count = (torch.zeros if read_back else torch.empty)(1, dtype=torch.int32, device=indptr.device)
     _lib.check(lib.hsg_rel_work(n, _lib.ptr(indptr), pmin, mult, _lib.ptr(work), cap, _lib.ptr(count), stream),
                "hsg_rel_work")
     return work, count
@@ -139,8 +153,6 @@ def build_relation(kind, src, dst, unit, tffrac=None, edtype=None):
     tf-idf box per edge following HiGraph.py:146-151: rows of ``_TFembed`` for dtype-0
     edges, :data:`ZERO_ROW` for any other typed edge (never written -> zeros).
     All inputs are tensors on one ROCm device; one 5-int readback gives the sizes."""
-    from . import _lib
-
     s_unit, d_unit = KINDS[kind]
     dev = src.device
     if dev.type != "cuda":
@@ -199,7 +211,6 @@ def edge_dst(rel):
 def attach_work_lists(d, n_src, n_dst, n_typed):
     """Add the CSR / CSC work lists (``dwork`` / ``swork``) of a relation's device arrays
     ``d`` when some segment is long enough to be split (hsg_rel_work)."""
-    from . import _lib
     lib = _lib.load()
     dev = d["indptr"].device
     with torch.cuda.device(dev):

@@ -15,27 +15,14 @@ inside a batch every document's slice holds the document's own relation plus fiv
 offsets (node, edge, source rank, destination rank, typed edge).  tests/resident_ref.py
 restates the assembly in numpy and pins it against ``graph.batch`` and the relation oracle.
 
-The store also hands the model its index structures with the batch (the *model view*,
-include/hsg_resident_model.h): the sentence node list, the sentences' token rows with their CNN
-row layout, the LSTM's document layout, the loss's document offsets and the tf-idf table index
-are functions of the picked documents too.  They are validated once per document at build and
-assembled by one more launch per batch, so the model's forward starts without the host-built
-indices (and the host waits) it otherwise begins with.  ``model_view=False`` is the batch
-without it.
-
-For multi-document examples the store can hand over HSumDocGraph's doc-side layouts too (the
-*doc view*, include/hsg_resident_hdsg.h: the sentence -> doc pair list, the supernode order, the
-native glue's CSRs and inverse lists), kept per document in local form and assembled by one
-launch; and it keeps the lengths of every segment longer than ``relation.PIECE_MIN``, from which
-the item count of a batch's work lists follows on the host (:func:`work_items`), so
-``hsg_rel_work`` runs without its read-back.  ``doc_view=False`` is the batch without both.
-
-A store that was handed the documents' word ids (``eval_words``) keeps them on the device in
-local form and hands the evaluation step its blocking operand with the batch (the *eval view*,
-include/hsg_resident_eval.h: ``G.eval_pack``, bit-equal to ``evalsel.pack_words(G.eval_words,
-counts)``, assembled by one launch), with the seen set sized from a per-store cache
-(:meth:`DocumentStore.seen_need`).  It is independent of the other two views;
-``eval_view=False`` is the batch without it.
+More of what the model and the evaluation build from a batch is a function of the picked
+documents too, so the store hands it over with the batch, as *views*: :class:`ModelView`,
+:class:`DocView`, :class:`EvalView`.  Each is one class holding all the store knows of it: what
+it validates and keeps per document at build (a document that cannot carry a view makes the
+store decline that view; nothing raises), its device columns, the running offsets it adds to a
+batch's one pinned copy (:func:`pack_parts`), and its one launch per batch with what that
+attaches to the graph.  ``DocumentStore._build`` and ``batch`` loop over ``store.views``;
+``model_view=False`` / ``doc_view=False`` / ``eval_view=False`` is the batch without that view.
 
 There is no fallback: a CPU device, a pick outside the store or a batch beyond
 ``hsg_res_supported`` raises.  Changing a dataset after its store was built is the caller's
@@ -44,6 +31,7 @@ business (the store does not look at the dataset again).
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -52,7 +40,7 @@ from . import _lib
 from .evalsel import WordPack
 from .graph import BatchedDGLGraph, Frame
 from .relation import HOT_KINDS, KINDS, Relation, attach_work_lists, build_relation
-from .relation import PIECE_MIN, PIECE_MULT
+from .relation import PIECE_MIN, _work_list, piece_params, work_list_capacity
 
 NODE, EDGE, SENT, NFAM = _lib.HSG_RES_NODE, _lib.HSG_RES_EDGE, _lib.HSG_RES_SENT, _lib.HSG_RES_NFAM
 SRC, DST, TYP = _lib.HSG_RES_SRC, _lib.HSG_RES_DST, _lib.HSG_RES_TYP
@@ -71,12 +59,19 @@ def _narrow(a, dtype, what, doc):
     return b
 
 
+def _pieces(piece_min, piece_mult):
+    """The two given, or ``relation.piece_params()``'s in place of a None."""
+    if piece_min is None or piece_mult is None:
+        pmin, mult = piece_params()
+        return pmin if piece_min is None else piece_min, mult if piece_mult is None else piece_mult
+    return piece_min, piece_mult
+
+
 def needs_work_list(n, n_typed, longest, piece_min=None, piece_mult=None):
     """``hsg_rel_work``'s rule on the host: does a CSR / CSC of ``n`` segments over ``n_typed``
     edges, the longest of ``longest`` edges, get a work list?  A segment is split when it is
     longer than ``P = max(PIECE_MIN, PIECE_MULT * ceil(n_typed / n))``."""
-    pmin = int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN))) if piece_min is None else piece_min
-    mult = int(_lib.path_option("HSG_PIECE_MULT", str(PIECE_MULT))) if piece_mult is None else piece_mult
+    pmin, mult = _pieces(piece_min, piece_mult)
     if n <= 0 or pmin <= 0:
         return False
     return longest > max(pmin, mult * (-(-n_typed // n)))
@@ -129,8 +124,7 @@ def work_items(n, n_typed, long_lens, piece_min=None, piece_mult=None, kept=PIEC
     with ``P = max(PIECE_MIN, PIECE_MULT * ceil(n_typed / n))`` -- or 0 when no segment exceeds
     ``P`` (no list).  Raises when ``piece_min`` is below ``kept``: shorter segments could then
     be split, and their lengths were not kept."""
-    pmin = int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN))) if piece_min is None else piece_min
-    mult = int(_lib.path_option("HSG_PIECE_MULT", str(PIECE_MULT))) if piece_mult is None else piece_mult
+    pmin, mult = _pieces(piece_min, piece_mult)
     if n <= 0 or pmin <= 0:
         return 0
     if pmin < kept:
@@ -418,6 +412,248 @@ def _device(device, allow_cpu=False):
     return device
 
 
+def _starts(counts):
+    """The exclusive prefix sums of ``counts`` and their total: int64 ``[len(counts) + 1]``."""
+    out = np.zeros(len(counts) + 1, np.int64)
+    np.cumsum(counts, out=out[1:])
+    return out
+
+
+def pack_parts(parts):
+    """What one pinned copy of a batch carries: ``parts`` (the pick list, then every active
+    view's running offsets) end to end as one int32 array, and the slice of each part in it."""
+    cuts, at = [], 0
+    for a in parts:
+        cuts.append(slice(at, at + len(a)))
+        at += len(a)
+    return np.concatenate(parts).astype(np.int32), cuts
+
+
+# ---------------------------------------------------------------------- views
+# What a store knows about one view of its batches, in one common shape: ``ok`` / ``reason``;
+# ``add(doc, no)`` per document at build (it declines and never raises; a view that declined is
+# not called again unless ``always``); ``finish(device)`` concatenates, uploads (``cols``) and fills ``cstruct``;
+# ``offsets(lib, slots, tot)`` gives the view's running sums over the sorted pick ([B + 1] int64
+# each, they ride in the batch's pinned copy) after its ``*_supported`` check; ``assemble(b, host,
+# dev)`` allocates the outputs, launches and attaches them to ``b.G``, ``host`` / ``dev`` being
+# those offsets as given and as they arrived on the device, ``b`` the batch's store, library,
+# slots, totals, sentence counts, allocator and launch operands.  ``needs``: the view this one is only attached with.
+class _View:
+    flag = needs = None               # ``flag``: batch()'s keyword, and the store's attribute
+    always = False                    # True: built and kept for a store that declined it too
+    checked = 1                       # the order in which batch() runs the ``*_supported`` checks
+
+    def __init__(self, *parts):
+        self.ok, self.reason = True, None
+        self.cols, self.cstruct = {}, None
+        self._parts = {k: [] for k in parts}          # per document, until finish()
+
+    def decline(self, reason):
+        self.ok, self.reason = False, reason
+
+    def keep(self, arrays):
+        for k, a in arrays.items():
+            self._parts[k].append(a)
+
+    def upload(self, arrays, device):
+        self.cols = {k: torch.from_numpy(np.ascontiguousarray(a)).to(device) for k, a in arrays.items()}
+        self._parts = None
+
+    def tensors(self):
+        return list(self.cols.values())
+
+
+class ModelView(_View):
+    """include/hsg_resident_model.h: the model's index structures (``G.model_inputs``, a
+    :class:`ModelInputs`, and the entries the model caches on the graph), so a forward starts
+    without the host-built indices and the host waits it otherwise begins with.  Host:
+    ``rows_of`` (CNN rows, ``sum(length + 1)``) and ``distinct`` (distinct non-zero tokens) per
+    document, ``max_token`` of the store -- kept, with the columns, for a store that declined the
+    view too, as they always were (``store.distinct``, ``store.nbytes``)."""
+    flag, always = "model_view", True
+
+    def __init__(self):
+        super().__init__("tok_len", "tok_row", "rows", "distinct")
+        self.max_token = 0
+
+    def add(self, doc, no):
+        reason = view_refusal(doc, no) if self.ok else None
+        if reason is not None:
+            self.decline(reason)
+        # per sentence its length and row offset (cnn._layout's rule)
+        words = np.asarray(doc.words)
+        length, pre, n_rows, _ = sentence_layout(words)
+        self.keep(dict(tok_len=length.astype(np.int32), tok_row=pre.astype(np.int32), rows=n_rows,
+                       distinct=int(np.count_nonzero(np.unique(words)))))
+        self.max_token = max(self.max_token, int(words.max()) if words.size else 0)
+
+    def finish(self, device):
+        p = self._parts
+        self.rows_of, self.distinct = np.asarray(p["rows"], np.int64), np.asarray(p["distinct"], np.int64)
+        self.upload({k: np.concatenate(p[k]) for k in ("tok_len", "tok_row")}, device)
+
+    def offsets(self, lib, slots, tot):
+        rowbase = _starts(self.rows_of[slots])
+        B, n_s, rows = len(slots), int(tot[SENT]), int(rowbase[-1])
+        if not lib.hsg_res_model_supported(B, n_s, int(tot[EDGE]), rows):
+            raise RuntimeError(f"batch of {B} documents, {n_s} sentences, {rows} token rows: "
+                               "beyond hsg_res_model_supported")
+        return [rowbase]
+
+    def assemble(self, b, host, dev):
+        G, new, p, i64, i32 = b.G, b.new, _lib.ptr, torch.int64, torch.int32
+        B, n_s, E, L = len(b.slots), int(b.tot[SENT]), int(b.tot[EDGE]), b.store.sent_len
+        t = dict(sent_nodes=new(n_s, i64), sent_ids=new((n_s, L), i64), sent_pos=new(n_s, i64),
+                 sent_len=new(n_s, i64), rowoff=new(n_s + 1, i32), doc_off=new(B + 1, i32),
+                 prev=new((n_s, 2), i64), tfidf_index=new(E, i64))
+        _lib.check(b.lib.hsg_res_model(b.cs, p(self.cols["tok_len"]), p(self.cols["tok_row"]), B, p(b.pick),
+                                       p(b.offs), p(dev[0]), n_s, E, *[p(v) for v in t.values()], b.st),
+                   "hsg_res_model")
+        glen = b.glen
+        G._set_view(ModelInputs(glen, host[0][B], 1 + int(self.distinct[b.slots].sum()), self.max_token, **t))
+        # under the keys HiGraph._cached uses; the word nodes are the W2S relation's sources
+        words = G._rel_cache[("rel", "W2S", str(G.device))].dev["src_nodes"]
+        for key, val in zip(VIEW_KEYS, (words, t["sent_nodes"], glen, t["tfidf_index"], t["doc_off"])):
+            G._rel_cache[(key, str(G.device))] = val
+
+
+class DocView(_View):
+    """include/hsg_resident_hdsg.h: the entries ``HiGraph._hdsg_layout`` and ``_hdsg_head_layout``
+    cache on the graph, from each document's local form of them; only attached with the model
+    view.  Host: ``docn`` (doc nodes) and ``pairs`` (sentence -> doc pairs) per document, and the
+    lengths of the segments longer than ``PIECE_MIN`` (``long_lens`` ``[kind][side]``, every
+    document's end to end, beginning at ``long_starts``), from which the view sizes a batch's
+    work lists on the host instead of reading their counts back."""
+    flag = "doc_view"
+
+    def __init__(self, model):
+        super().__init__(*[k for fam in HDSG_COLUMNS.values() for k in fam])
+        self.needs = model
+        self._long = [[[], []] for _ in HOT_KINDS]
+
+    def add(self, doc, no):
+        reason, local = doc_view_local(doc, no)
+        if reason is not None:
+            return self.decline(reason)
+        self.keep(local)
+        for q, sides in enumerate(long_segments(doc)):
+            for side, lens in enumerate(sides):
+                self._long[q][side].append(lens)
+
+    def finish(self, device):
+        p = self._parts
+        self.docn = np.asarray([len(a) for a in p["inv_cnt"]], np.int64)
+        self.pairs = np.asarray([len(a) for a in p["pair_s"]], np.int64)
+        self.long_lens = [[np.concatenate(v) for v in sides] for sides in self._long]
+        self.long_starts = [[_starts([len(a) for a in v]) for v in sides] for sides in self._long]
+        self._long = None
+        self.upload(dict({k: np.concatenate(v) for k, v in p.items()}, dstart=_starts(self.docn),
+                         pstart=_starts(self.pairs)), device)
+        self.cstruct = _lib.HsgResHdsgCols(**{k: _lib.ptr(v) for k, v in self.cols.items()})
+
+    def offsets(self, lib, slots, tot):
+        docbase, pairbase = _starts(self.docn[slots]), _starts(self.pairs[slots])
+        B, n_dn, n_pr = len(slots), int(docbase[-1]), int(pairbase[-1])
+        if not lib.hsg_res_hdsg_supported(B, int(tot[SENT]), n_dn, n_pr, int(tot[DST(0)])):
+            raise RuntimeError(f"batch of {B} documents, {n_dn} doc nodes, {n_pr} sentence-doc pairs: "
+                               "beyond hsg_res_hdsg_supported")
+        return [docbase, pairbase]
+
+    def work_lists(self, b, q, d, ns, ndst, nt, pieces):
+        """Relation ``q``'s work lists onto its arrays ``d`` with each side's item count from the
+        kept segment lengths: the unchanged ``hsg_rel_work`` into today's buffer, sliced by that
+        count; nothing is read back.  False (nothing done) when shorter segments could split."""
+        if pieces[0] < PIECE_MIN:
+            return False
+        for key, side, n, ptr_key in (("dwork", 0, ndst, "indptr"), ("swork", 1, ns, "cindptr")):
+            a, st = self.long_lens[q][side], self.long_starts[q][side]
+            items = work_items(n, nt, np.concatenate([a[st[s]:st[s + 1]] for s in b.slots]), *pieces)
+            cap = work_list_capacity(n, nt, pieces[0])
+            if items > 0 and not n <= items <= cap:
+                raise AssertionError(f"work list of {items} items for {n} segments: outside [n, {cap}]")
+            if items > 0:
+                d[key] = _work_list(b.lib, n, d[ptr_key], nt, b.st, read_back=False, pieces=pieces)[0][:5 * items]
+        return True
+
+    def assemble(self, b, host, dev):
+        from .head import HeadLayout
+        G, new, p, B = b.G, b.new, _lib.ptr, len(b.slots)
+        n_s, n_dn, n_pr, n_su = int(b.tot[SENT]), int(host[0][B]), int(host[1][B]), int(b.tot[DST(0)])
+        sizes = dict(pair_s=n_pr, pair_d=n_pr, super_pos=n_su, sent_super=n_s, doc_super=n_s, super_src=n_su,
+                     doc_ptr=n_dn + 1, doc_sent=n_pr, sent_ptr=n_s + 1, sent_doc=n_pr, sent_row=n_s,
+                     doc_row=n_dn, sup_sent=n_su, sup_ptr=n_su + 1, sup_list=n_s)
+        lay = {k: new(sizes[k], torch.int64) for k in HDSG_DICT}
+        inv_cnt = new(n_dn, torch.float32)
+        lists = {k: new(sizes[k], torch.int32) for k in HDSG_HEAD}
+        _lib.check(b.lib.hsg_res_hdsg(b.cs, ctypes.byref(self.cstruct), B, p(b.pick), p(b.offs), p(dev[0]),
+                                      p(dev[1]), n_s, n_dn, n_pr, n_su, *[p(v) for v in lay.values()],
+                                      p(inv_cnt), *[p(v) for v in lists.values()], b.st), "hsg_res_hdsg")
+        # under the keys HiGraph._hdsg_layout / _hdsg_head_layout use
+        G._rel_cache[(HDSG_KEYS[0], str(G.device))] = dict(lay, inv_cnt=inv_cnt, n_docs=n_dn)
+        G._rel_cache[(HDSG_KEYS[1], str(G.device))] = HeadLayout.prebuilt(n_s, n_dn, n_su, inv_cnt, **lists)
+
+
+class EvalView(_View):
+    """include/hsg_resident_eval.h: the evaluation step's blocking operand (``G.eval_pack``, a
+    :class:`ResidentWordPack` bit-equal to ``evalsel.pack_words(G.eval_words, counts)``) from each
+    document's local ``(ptr, ids)``; a store built without ``eval_words``, or with an entry of
+    another form than one ``word_ids`` pair, declines it.  Independent of the other views.  Host:
+    ``words_of`` (words per document) and what sizes the seen set (:meth:`seen_need`)."""
+    flag, checked = "eval_view", 0
+
+    def __init__(self, eval_words):
+        super().__init__("wend", "wid", "lens")
+        self._words, self._need = eval_words, {}
+        if eval_words is None:
+            self.decline("the store was built without eval_words")
+
+    def add(self, doc, no):
+        ew = "it has no eval_words entry"
+        if no < len(self._words):
+            ew = eval_view_local(self._words[no], len(doc.sent_nodes))
+        if isinstance(ew, str):
+            return self.decline(f"document {no}: {ew}")
+        self.keep(ew)
+
+    def finish(self, device):
+        p = self._parts
+        self.words_of = np.asarray([len(a) for a in p["wid"]], np.int64)
+        # every document's words per row sorted descending, each row's document and its position
+        # inside it (seen_need)
+        self._seen = seen_columns(p["lens"])
+        self.upload(dict(wstart=_starts(self.words_of), wend=np.concatenate(p["wend"]), wid=np.concatenate(p["wid"])),
+                    device)
+        self.cstruct = _lib.HsgResEvalCols(**{k: _lib.ptr(v) if v.numel() else None for k, v in self.cols.items()})
+
+    def seen_need(self, n_win, m):
+        """Per document of the store, :func:`seen_need` for windows of ``n_win`` words and ``m``
+        chosen sentences: int64 ``[n_docs]``, computed once per pair and kept."""
+        key = (int(n_win), int(m))
+        if key not in self._need:
+            if not self.ok:
+                raise RuntimeError("the store declined the eval view: " + self.reason)
+            self._need[key] = seen_need(*self._seen, len(self.words_of), *key)
+        return self._need[key]
+
+    def offsets(self, lib, slots, tot):
+        wordbase = _starts(self.words_of[slots])
+        B, n_s, n_w = len(slots), int(tot[SENT]), int(wordbase[-1])
+        if not lib.hsg_res_eval_supported(B, n_s, n_w):
+            raise RuntimeError(f"batch of {B} documents, {n_s} sentences, {n_w} words: beyond "
+                               "hsg_res_eval_supported")
+        return [wordbase]
+
+    def assemble(self, b, host, dev):
+        p, B, n_s, n_w = _lib.ptr, len(b.slots), int(b.tot[SENT]), int(host[0][-1])
+        pack = b.new(n_s + 1 + max(n_w, 1), torch.int32)
+        _lib.check(b.lib.hsg_res_eval(b.cs, ctypes.byref(self.cstruct), B, p(b.pick), p(b.offs), p(dev[0]), n_s,
+                                      n_w, p(pack), b.st), "hsg_res_eval")
+        b.G.eval_pack = ResidentWordPack(pack, n_s, B, n_w, list(b.glen), b.store, b.slots)
+
+
+STORE_COLUMNS = ("unit", "ndtype", "id", "sent_rank", "words", "label", "src", "dst", "tffrac", "edtype")
+
+
 class DocumentStore:
     """Every document of a dataset, on the device (see the module docstring)."""
 
@@ -464,186 +700,133 @@ class DocumentStore:
     @classmethod
     def _build(cls, chunks, device, indices, eval_words):
         self = cls(device)
-        dev = self.device
-        counts, longest, bases = [], [], []
-        host = {k: [] for k in ("unit", "ndtype", "src", "dst", "tffrac", "edtype")}
-        cols = {k: [] for k in ("unit", "ndtype", "id", "sent_rank", "words", "label", "src", "dst", "tffrac", "edtype")}
-        rels = [{k: [] for k in REL_ARRAYS} for _ in HOT_KINDS]
+        model = ModelView()
+        self.views = {v.flag: v for v in (model, DocView(model), EvalView(eval_words))}     # in launch order
         self.sent_len = self.label_len = None
-        self.model_view, self.model_view_reason = True, None
-        view = {k: [] for k in ("tok_len", "tok_row")}
-        rows_of, distinct, self.max_token = [], [], 0
-        # the doc view (include/hsg_resident_hdsg.h): per document the local form of the doc-side
-        # index structures; the segments longer than PIECE_MIN, which size a batch's work lists
-        self.doc_view, self.doc_view_reason = True, None
-        hdsg = {k: [] for fam in HDSG_COLUMNS.values() for k in fam}
-        long_lens = [[[], []] for _ in HOT_KINDS]
-        # the eval view (include/hsg_resident_eval.h): per document the local (ptr, ids) of its
-        # eval_words entry; an entry of another form makes the store decline the view
-        self.eval_view = eval_words is not None
-        self.eval_view_reason = None if self.eval_view else "the store was built without eval_words"
-        ev = {k: [] for k in ("wend", "wid", "lens")}
-        n_seen = 0
+        acc = SimpleNamespace(counts=[], longest=[], bases=[], cols={k: [] for k in STORE_COLUMNS},
+                              host={k: [] for k in ("unit", "ndtype", "src", "dst", "tffrac", "edtype")},
+                              rels=[{k: [] for k in REL_ARRAYS} for _ in HOT_KINDS])
         for docs in chunks:
             if not docs:
                 continue
             base = np.zeros(NFAM, np.int64)
-            part = {k: [] for k in cols}
+            part = {k: [] for k in STORE_COLUMNS}
             for doc in docs:
-                no = n_seen
-                n_seen += 1
-                cnt, lng = doc_counts(doc)
-                n, N = int(cnt[NODE]), int(cnt[SENT])
-                words, label = np.asarray(doc.words), np.asarray(doc.label)
-                if words.ndim != 2 or label.ndim != 2 or len(words) != N or len(label) != N:
-                    raise ValueError(f"document {no}: 'words' / 'label' are not [sentences, width]")
-                if self.sent_len is None:
-                    self.sent_len, self.label_len = int(words.shape[1]), int(label.shape[1])
-                if (words.shape[1], label.shape[1]) != (self.sent_len, self.label_len):
-                    raise ValueError(f"document {no}: sentence rows of another width than the store's")
-                if not np.array_equal(np.asarray(doc.position).reshape(-1), np.arange(1, N + 1)):
-                    raise ValueError(f"document {no}: 'position' is not 1..N (the store does not keep it)")
-                sn = np.asarray(doc.sent_nodes, np.int64)
-                if len(np.unique(sn)) != N or (N and (sn.min() < 0 or sn.max() >= n)):
-                    raise ValueError(f"document {no}: sentence nodes repeat or lie outside the document")
-                if cnt[EDGE] and (min(doc.src.min(), doc.dst.min()) < 0 or max(doc.src.max(), doc.dst.max()) >= n):
-                    raise ValueError(f"document {no}: an edge references a node outside the document")
-                if base[NODE] + n > I32_MAX or base[EDGE] + cnt[EDGE] > I32_MAX:
-                    raise ValueError("a build chunk beyond 2^31 - 1 nodes or edges: use a smaller chunk")
-                rank = np.full(n, -1, np.int32)
-                rank[sn] = np.arange(N, dtype=np.int32)
-                u8 = {k: _narrow(getattr(doc, k), np.uint8, k, no) for k in ("unit", "ndtype", "tffrac", "edtype")}
-                src, dst = _narrow(doc.src, np.int32, "src", no), _narrow(doc.dst, np.int32, "dst", no)
-                for k in ("unit", "ndtype", "tffrac", "edtype"):
-                    host[k].append(u8[k])
-                    part[k].append(u8[k])
-                host["src"].append(src)
-                host["dst"].append(dst)
-                part["src"].append(src + np.int32(base[NODE]))
-                part["dst"].append(dst + np.int32(base[NODE]))
-                part["id"].append(_narrow(doc.wid, np.int32, "id", no))
-                part["sent_rank"].append(rank)
-                part["words"].append(_narrow(words, np.int32, "words", no).reshape(-1))
-                part["label"].append(_narrow(label, np.uint8, "label", no).reshape(-1))
-                # the model view: per sentence its length and row offset (cnn._layout's rule), per
-                # document the row count and the distinct tokens; a document that cannot carry
-                # the view makes the store decline it, nothing raises here
-                length, pre, n_rows, _ = sentence_layout(words)
-                view["tok_len"].append(length.astype(np.int32))
-                view["tok_row"].append(pre.astype(np.int32))
-                rows_of.append(n_rows)
-                distinct.append(int(np.count_nonzero(np.unique(words))))
-                self.max_token = max(self.max_token, int(words.max()) if words.size else 0)
-                if self.model_view:
-                    self.model_view_reason = view_refusal(doc, no)
-                    self.model_view = self.model_view_reason is None
-                if self.doc_view:
-                    self.doc_view_reason, local = doc_view_local(doc, no)
-                    self.doc_view = self.doc_view_reason is None
-                    for k, a in (local or {}).items():
-                        hdsg[k].append(a)
-                if self.eval_view:
-                    ew = eval_view_local(eval_words[no], N) if no < len(eval_words) else "it has no eval_words entry"
-                    if isinstance(ew, str):
-                        self.eval_view, self.eval_view_reason = False, f"document {no}: {ew}"
-                    else:
-                        for k, a in ew.items():
-                            ev[k].append(a)
-                for q, sides in enumerate(long_segments(doc)):
-                    for side, lens in enumerate(sides):
-                        long_lens[q][side].append(lens)
-                counts.append(cnt)
-                longest.append(lng)
-                bases.append(base.copy())
+                no = len(acc.counts)
+                cnt, lng = self._add_document(doc, no, base, acc.host, part)
+                for v in self.views.values():
+                    if v.ok or v.always:        # a view that declined does no more work
+                        v.add(doc, no)
+                acc.counts.append(cnt)
+                acc.longest.append(lng)
+                acc.bases.append(base.copy())
                 base += cnt
-            cat = {k: torch.from_numpy(np.concatenate(v)).to(dev) for k, v in part.items()}
-            for k, v in cat.items():
-                cols[k].append(v)
-            # the chunk's relations, by today's builder; chunk-relative values are kept as they are
-            for q, kind in enumerate(HOT_KINDS):
-                rel = build_relation(kind, cat["src"], cat["dst"], cat["unit"], cat["tffrac"], cat["edtype"])
-                if (rel.n_src, rel.n_dst, rel.n_typed) != (base[SRC(q)], base[DST(q)], base[TYP(q)]):
-                    raise RuntimeError(f"{kind}: hsg_rel_build disagrees with the host counts of the chunk")
-                d = rel.dev
-                for k in REL_ARRAYS:
-                    a = d[k][:rel.n_dst] if k == "indptr" else d[k][:rel.n_src] if k == "cindptr" else d[k]
-                    rels[q][k].append(a.to(torch.uint8 if k == "tf" else torch.int32))
-        if not counts:
+            self._upload_chunk(part, base, acc)
+        self._close(acc, indices, eval_words)
+        return self
+
+    def _add_document(self, doc, no, base, host, part):
+        """The store's own step for document ``no``, ``base`` of its families into its chunk:
+        validation, narrowing, the host copies and the chunk's columns.  Its counts and longest
+        segments (:func:`doc_counts`)."""
+        cnt, lng = doc_counts(doc)
+        n, N = int(cnt[NODE]), int(cnt[SENT])
+        words, label = np.asarray(doc.words), np.asarray(doc.label)
+        if words.ndim != 2 or label.ndim != 2 or len(words) != N or len(label) != N:
+            raise ValueError(f"document {no}: 'words' / 'label' are not [sentences, width]")
+        if self.sent_len is None:
+            self.sent_len, self.label_len = int(words.shape[1]), int(label.shape[1])
+        if (words.shape[1], label.shape[1]) != (self.sent_len, self.label_len):
+            raise ValueError(f"document {no}: sentence rows of another width than the store's")
+        if not np.array_equal(np.asarray(doc.position).reshape(-1), np.arange(1, N + 1)):
+            raise ValueError(f"document {no}: 'position' is not 1..N (the store does not keep it)")
+        sn = np.asarray(doc.sent_nodes, np.int64)
+        if len(np.unique(sn)) != N or (N and (sn.min() < 0 or sn.max() >= n)):
+            raise ValueError(f"document {no}: sentence nodes repeat or lie outside the document")
+        if cnt[EDGE] and (min(doc.src.min(), doc.dst.min()) < 0 or max(doc.src.max(), doc.dst.max()) >= n):
+            raise ValueError(f"document {no}: an edge references a node outside the document")
+        if base[NODE] + n > I32_MAX or base[EDGE] + cnt[EDGE] > I32_MAX:
+            raise ValueError("a build chunk beyond 2^31 - 1 nodes or edges: use a smaller chunk")
+        rank = np.full(n, -1, np.int32)
+        rank[sn] = np.arange(N, dtype=np.int32)
+        u8 = {k: _narrow(getattr(doc, k), np.uint8, k, no) for k in ("unit", "ndtype", "tffrac", "edtype")}
+        src, dst = _narrow(doc.src, np.int32, "src", no), _narrow(doc.dst, np.int32, "dst", no)
+        for k in ("unit", "ndtype", "tffrac", "edtype"):
+            host[k].append(u8[k])
+            part[k].append(u8[k])
+        host["src"].append(src)
+        host["dst"].append(dst)
+        part["src"].append(src + np.int32(base[NODE]))
+        part["dst"].append(dst + np.int32(base[NODE]))
+        part["id"].append(_narrow(doc.wid, np.int32, "id", no))
+        part["sent_rank"].append(rank)
+        part["words"].append(_narrow(words, np.int32, "words", no).reshape(-1))
+        part["label"].append(_narrow(label, np.uint8, "label", no).reshape(-1))
+        return cnt, lng
+
+    def _upload_chunk(self, part, base, acc):
+        """One build chunk: its columns to the device, and its relations by today's builder
+        (chunk-relative values are kept as they are).  ``base``: the chunk's family totals."""
+        cat = {k: torch.from_numpy(np.concatenate(v)).to(self.device) for k, v in part.items()}
+        for k, v in cat.items():
+            acc.cols[k].append(v)
+        for q, kind in enumerate(HOT_KINDS):
+            rel = build_relation(kind, cat["src"], cat["dst"], cat["unit"], cat["tffrac"], cat["edtype"])
+            if (rel.n_src, rel.n_dst, rel.n_typed) != (base[SRC(q)], base[DST(q)], base[TYP(q)]):
+                raise RuntimeError(f"{kind}: hsg_rel_build disagrees with the host counts of the chunk")
+            d = rel.dev
+            for k in REL_ARRAYS:
+                a = d[k][:rel.n_dst] if k == "indptr" else d[k][:rel.n_src] if k == "cindptr" else d[k]
+                acc.rels[q][k].append(a.to(torch.uint8 if k == "tf" else torch.int32))
+
+    def _close(self, acc, indices, eval_words):
+        """The closing step of a build: the host tables, the views, the device struct."""
+        if not acc.counts:
             raise ValueError("an empty document store")
-        self._docs = len(counts)
-        self.counts = np.stack(counts)                                    # [n_docs, NFAM]
-        self.longest = np.stack(longest)                                  # [n_docs, kind, CSR / CSC]
+        dev = self.device
+        self._docs = len(acc.counts)
+        self.counts = np.stack(acc.counts)                                # [n_docs, NFAM]
+        self.longest = np.stack(acc.longest)                              # [n_docs, kind, CSR / CSC]
         self.starts = np.zeros((NFAM, self._docs + 1), np.int64)
         self.starts[:, 1:] = np.cumsum(self.counts, 0).T
-        self.bases = np.ascontiguousarray(np.stack(bases).T)              # [NFAM, n_docs]
+        self.bases = np.ascontiguousarray(np.stack(acc.bases).T)          # [NFAM, n_docs]
         self.indices = list(range(self._docs)) if indices is None else [int(i) for i in indices]
         if len(self.indices) != self._docs or len(set(self.indices)) != self._docs:
             raise ValueError("indices: one distinct dataset index per document")
         self._slot_of = {ix: s for s, ix in enumerate(self.indices)}
         self.eval_words = None if eval_words is None else list(eval_words)
-        self._host = {k: np.concatenate(v) for k, v in host.items()}
-        self._cols = {k: torch.cat(v) for k, v in cols.items()}
-        self._rels = [{k: torch.cat(v) for k, v in r.items()} for r in rels]
-        self.rows_of = np.asarray(rows_of, np.int64)                     # [n_docs] CNN rows: sum(length + 1)
-        self.distinct = np.asarray(distinct, np.int64)                   # [n_docs] distinct non-zero tokens
-        self._view_cols = {k: torch.from_numpy(np.concatenate(v)).to(dev) for k, v in view.items()}
-        # [kind][side]: the kept segment lengths of every document end to end, and where each begins
-        self.long_lens = [[np.concatenate(v) for v in sides] for sides in long_lens]
-        self.long_starts = [[np.concatenate([[0], np.cumsum([len(a) for a in v])]).astype(np.int64) for v in sides]
-                            for sides in long_lens]
-        self.doc_view = self.doc_view and self.model_view
-        if self.doc_view_reason is None and not self.model_view:
-            self.doc_view_reason = "the store declined the model view: " + self.model_view_reason
-        self._hdsg_cols, self._hdsg_cstruct = {}, None
-        if self.doc_view:
-            self.docn = np.asarray([len(a) for a in hdsg["inv_cnt"]], np.int64)      # [n_docs] doc nodes
-            self.pairs = np.asarray([len(a) for a in hdsg["pair_s"]], np.int64)      # [n_docs] sentence -> doc pairs
-            starts = lambda c: torch.from_numpy(np.concatenate([[0], np.cumsum(c)]).astype(np.int64)).to(dev)
-            self._hdsg_cols = {k: torch.from_numpy(np.ascontiguousarray(np.concatenate(v))).to(dev)
-                               for k, v in hdsg.items()}
-            self._hdsg_cols.update(dstart=starts(self.docn), pstart=starts(self.pairs))
-            self._hdsg_cstruct = _lib.HsgResHdsgCols(**{k: _lib.ptr(v) for k, v in self._hdsg_cols.items()})
-        self._eval_cols, self._eval_cstruct, self._need = {}, None, {}
-        if self.eval_view:
-            self.words_of = np.asarray([len(a) for a in ev["wid"]], np.int64)       # [n_docs] words
-            wstart = np.concatenate([[0], np.cumsum(self.words_of)]).astype(np.int64)
-            flat = lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dt)
-            self._eval_cols = {k: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                               for k, a in (("wstart", wstart), ("wend", flat(ev["wend"], np.int32)),
-                                            ("wid", flat(ev["wid"], np.int32)))}
-            self._eval_cstruct = _lib.HsgResEvalCols(**{k: _lib.ptr(v) if v.numel() else None
-                                                        for k, v in self._eval_cols.items()})
-            # what sizes the seen set: every document's words per row sorted descending, each
-            # row's document and its position inside it (seen_need)
-            self._lens_desc, self._row_doc, self._row_rank = seen_columns(ev["lens"])
+        self._host = {k: np.concatenate(v) for k, v in acc.host.items()}
+        self._cols = {k: torch.cat(v) for k, v in acc.cols.items()}
+        self._rels = [{k: torch.cat(v) for k, v in r.items()} for r in acc.rels]
+        for v in self.views.values():
+            if v.ok and v.needs is not None and not v.needs.ok:
+                v.decline(f"the store declined the {v.needs.flag.replace('_', ' ')}: {v.needs.reason}")
+            if v.ok or v.always:
+                v.finish(dev)
+            setattr(self, v.flag, v.ok)                 # store.model_view, store.model_view_reason, ...
+            setattr(self, v.flag + "_reason", v.reason)
         self._starts_d = torch.from_numpy(self.starts).to(dev)
         self._bases_d = torch.from_numpy(self.bases).to(dev)
         p = _lib.ptr
         self._cstruct = _lib.HsgResStore(
             self._docs, p(self._starts_d), p(self._bases_d), self.sent_len, self.label_len,
-            *[p(self._cols[k]) for k in ("unit", "ndtype", "id", "sent_rank", "words", "label", "src", "dst",
-                                         "tffrac", "edtype")],
+            *[p(self._cols[k]) for k in STORE_COLUMNS],
             (_lib.HsgResRel * 2)(*[_lib.HsgResRel(*[p(r[k]) for k in REL_ARRAYS]) for r in self._rels]))
         torch.cuda.synchronize(dev)        # the build's host arrays may go once the uploads are done
-        return self
 
     def __len__(self):
         return self._docs
 
-    def _tensors(self):
-        return list(self._cols.values()) + list(self._view_cols.values()) + list(self._hdsg_cols.values()) + \
-            list(self._eval_cols.values()) + [t for r in self._rels for t in r.values()] + \
-            [self._starts_d, self._bases_d]
+    distinct = property(lambda self: self.views["model_view"].distinct)
+    words_of = property(lambda self: self.views["eval_view"].words_of)
 
     def seen_need(self, n_win, m):
-        """Per document of the store, :func:`seen_need` for windows of ``n_win`` words and ``m``
-        chosen sentences: int64 ``[n_docs]``, computed once per pair and kept."""
-        key = (int(n_win), int(m))
-        if key not in self._need:
-            if not self.eval_view:
-                raise RuntimeError("the store declined the eval view: " + self.eval_view_reason)
-            self._need[key] = seen_need(self._lens_desc, self._row_doc, self._row_rank, self._docs, *key)
-        return self._need[key]
+        """:meth:`EvalView.seen_need`."""
+        return self.views["eval_view"].seen_need(n_win, m)
+
+    def _tensors(self):
+        return list(self._cols.values()) + [t for v in self.views.values() for t in v.tensors()] + \
+            [t for r in self._rels for t in r.values()] + [self._starts_d, self._bases_d]
 
     @property
     def nbytes(self):
@@ -679,53 +862,24 @@ class DocumentStore:
         except KeyError as e:
             raise IndexError(f"document {e.args[0]} is not in the store") from None
 
-    def _long(self, q, side, slots):
-        """The kept segment lengths (CSR: side 0, CSC: side 1) of kind ``q`` of the picked documents."""
-        a, st = self.long_lens[q][side], self.long_starts[q][side]
-        return np.concatenate([a[st[s]:st[s + 1]] for s in slots])
-
-    def _sized_work_list(self, lib, n, indptr, n_typed, items, st):
-        """One side's work list with its item count known on the host: the unchanged
-        ``hsg_rel_work`` into today's buffer, sliced by ``items``; nothing is read back."""
-        pmin = int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN)))
-        mult = int(_lib.path_option("HSG_PIECE_MULT", str(PIECE_MULT)))
-        cap = n + 2 * n_typed // pmin + 1
-        if not n <= items <= cap:
-            raise AssertionError(f"work list of {items} items for {n} segments: outside [n, {cap}]")
-        work = torch.empty(5 * cap, dtype=torch.int32, device=self.device)
-        count = torch.empty(1, dtype=torch.int32, device=self.device)          # written, never read
-        _lib.check(lib.hsg_rel_work(n, _lib.ptr(indptr), pmin, mult, _lib.ptr(work), cap, _lib.ptr(count), st),
-                   "hsg_rel_work")
-        return work[:5 * items]
-
     def batch(self, indices, model_view=None, doc_view=None, eval_view=None):
         """``(G, index)`` as ``graph_collate_fn`` gives them for the same documents: sorted by
         sentence count (descending, ties in the order given), ``G`` on the device.
 
-        ``model_view``: None (the store's default, :attr:`MODEL_VIEW`), True or False -- whether
-        the batch carries the model's index structures (``G.model_inputs`` and the entries the
-        model caches on the graph), assembled by one more launch.  A store that declined the
-        view at build (``store.model_view`` False, ``store.model_view_reason``) never attaches
-        it.  False is the batch without it, bit for bit.
-
-        ``doc_view``: None (:attr:`DOC_VIEW`), True or False -- whether a batch with the model
-        view also carries HSumDocGraph's doc-side layouts (the entries ``HiGraph._hdsg_layout``
-        and ``_hdsg_head_layout`` cache on the graph), assembled by one more launch, and has its
-        work lists sized on the host instead of read back.  A store that declined it
-        (``store.doc_view`` False, ``store.doc_view_reason``) never attaches it.  False is
-        today's batch, bit for bit, read-back included.
-
-        ``eval_view``: None (:attr:`EVAL_VIEW`), True or False -- whether the batch carries the
-        evaluation step's word pack (``G.eval_pack``, an ``evalsel.WordPack`` on the device that
-        is bit-equal to ``pack_words(G.eval_words, counts)`` and sizes the seen set from the
-        store's cache), assembled by one more launch; independent of the other two views.  A
-        store built without ``eval_words``, or with entries of another form than one
-        ``word_ids`` pair per document (``store.eval_view`` False, ``store.eval_view_reason``),
-        never attaches it.  False is today's batch, bit for bit; ``G.eval_words`` is attached
-        either way."""
-        view = self.model_view and (self.MODEL_VIEW if model_view is None else bool(model_view))
-        dview = view and self.doc_view and (self.DOC_VIEW if doc_view is None else bool(doc_view))
-        eview = self.eval_view and (self.EVAL_VIEW if eval_view is None else bool(eval_view))
+        ``model_view``, ``doc_view``, ``eval_view``: None (the store's default, :attr:`MODEL_VIEW`,
+        :attr:`DOC_VIEW`, :attr:`EVAL_VIEW`), True or False -- whether the batch carries that
+        view (:class:`ModelView`, :class:`DocView`, :class:`EvalView`), each assembled by one more
+        launch.  A view the store declined at build (``store.model_view`` False,
+        ``store.model_view_reason``, and so on) is never attached, nor is one without the view
+        it needs: the doc view rides on the model view; the evaluation's is independent of both.
+        With the doc view the batch's work lists are sized on the host instead of read back.
+        False is the batch without the view, bit for bit (read-back included);
+        ``G.eval_words`` is attached either way."""
+        want, active = dict(model_view=model_view, doc_view=doc_view, eval_view=eval_view), []
+        for v in self.views.values():
+            on = getattr(self, v.flag.upper()) if want[v.flag] is None else bool(want[v.flag])
+            if v.ok and on and (v.needs is None or v.needs in active):
+                active.append(v)
         slots = self.slots_of(indices)
         B = len(slots)
         if B < 1:
@@ -739,52 +893,15 @@ class DocumentStore:
         new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         i32, i64, f32 = torch.int32, torch.int64, torch.float32
         L, M = self.sent_len, self.label_len
-        n_s = int(tot[SENT])
-        if eview:
-            # the word running offsets, summed on the host from the kept counts, ride in the
-            # pinned copy that carries the pick list
-            wordbase = np.zeros(B + 1, np.int64)
-            np.cumsum(self.words_of[slots], out=wordbase[1:])
-            n_w = int(wordbase[B])
-            if not lib.hsg_res_eval_supported(B, n_s, n_w):
-                raise RuntimeError(f"batch of {B} documents, {n_s} sentences, {n_w} words: beyond "
-                                   "hsg_res_eval_supported")
+        # every active view's running offsets, summed on the host from the kept counts, ride behind
+        # the pick list in one small pinned copy, not waited for (the pinned block is recycled
+        # stream-safely)
+        host = {v: v.offsets(lib, slots, tot) for v in sorted(active, key=lambda v: v.checked)}
+        flat, cuts = pack_parts([slots] + [a for v in active for a in host[v]])
+        pieces = piece_params()
         with torch.cuda.device(dev):
-            # one small pinned copy, not waited for (the pinned block is recycled stream-safely)
-            if view:
-                # the per-document CNN row offsets, summed on the host from the kept counts, ride
-                # behind the pick list in the same pinned copy
-                rowbase = np.zeros(B + 1, np.int64)
-                np.cumsum(self.rows_of[slots], out=rowbase[1:])
-                if not lib.hsg_res_model_supported(B, n_s, E, int(rowbase[B])):
-                    raise RuntimeError(f"batch of {B} documents, {n_s} sentences, {int(rowbase[B])} token rows: "
-                                       "beyond hsg_res_model_supported")
-                host = [slots, rowbase]
-                if dview:
-                    # the doc-node and pair running offsets ride in the same copy
-                    docbase, pairbase = np.zeros(B + 1, np.int64), np.zeros(B + 1, np.int64)
-                    np.cumsum(self.docn[slots], out=docbase[1:])
-                    np.cumsum(self.pairs[slots], out=pairbase[1:])
-                    n_dn, n_pr, n_su = int(docbase[B]), int(pairbase[B]), int(tot[DST(0)])
-                    if not lib.hsg_res_hdsg_supported(B, n_s, n_dn, n_pr, n_su):
-                        raise RuntimeError(f"batch of {B} documents, {n_dn} doc nodes, {n_pr} sentence-doc pairs: "
-                                           "beyond hsg_res_hdsg_supported")
-                    host += [docbase, pairbase]
-                if eview:
-                    host.append(wordbase)
-                both = torch.from_numpy(np.concatenate(host).astype(np.int32))
-                both = both.pin_memory().to(dev, non_blocking=True)
-                pick, rowbase_d = both[:B], both[B:2 * B + 1]
-                if dview:
-                    docbase_d, pairbase_d = both[2 * B + 1:3 * B + 2], both[3 * B + 2:4 * B + 3]
-                if eview:
-                    wordbase_d = both[len(both) - (B + 1):]
-            elif eview:
-                both = torch.from_numpy(np.concatenate([slots, wordbase]).astype(np.int32))
-                both = both.pin_memory().to(dev, non_blocking=True)
-                pick, wordbase_d = both[:B], both[B:]
-            else:
-                pick = torch.from_numpy(slots.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+            both = torch.from_numpy(flat).pin_memory().to(dev, non_blocking=True)
+            pick, *arrived = [both[c] for c in cuts]
             offs = new(NFAM * (B + 1), i64)
             st = _lib.stream_of(offs)
             cs = ctypes.byref(self._cstruct)
@@ -803,12 +920,14 @@ class DocumentStore:
             G._nframe.cols, G._ef.cols = nd, ed
             G._dev_src, G._dev_dst = src, dst
             G.batch_size = B
-            G.batch_num_nodes = [int(x) for x in self.counts[slots, NODE]]
-            G.batch_num_edges = [int(x) for x in self.counts[slots, EDGE]]
+            G.batch_num_nodes = self.counts[slots, NODE].tolist()
+            G.batch_num_edges = self.counts[slots, EDGE].tolist()
             G._origin = (self, slots)
             G._h_src = G._h_dst = None                 # formed from the store on first use
             G._host_cols.update(self._host_node_columns(slots))
             G.resident_work_lists = {}
+            b = SimpleNamespace(store=self, G=G, lib=lib, cs=cs, slots=slots, tot=tot, pick=pick, offs=offs, st=st,
+                                new=new, glen=self.counts[slots, SENT].tolist())     # the batch, as the views see it
             for q, kind in enumerate(HOT_KINDS):
                 ns, ndst, nt = int(tot[SRC(q)]), int(tot[DST(q)]), int(tot[TYP(q)])
                 d = dict(indptr=new(ndst + 1, i32), src=new(nt, i32), tf=new(nt, torch.uint8), eid=new(nt, i64),
@@ -817,50 +936,15 @@ class DocumentStore:
                 _lib.check(lib.hsg_res_relation(cs, q, B, p(pick), p(offs), ns, ndst, nt,
                                                 *[p(d[k]) for k in REL_ARRAYS], st), "hsg_res_relation")
                 lng = self.longest[slots, q].max(0)
-                need = needs_work_list(ndst, nt, int(lng[0])) or needs_work_list(ns, nt, int(lng[1]))
+                need = needs_work_list(ndst, nt, int(lng[0]), *pieces) or needs_work_list(ns, nt, int(lng[1]), *pieces)
                 G.resident_work_lists[kind] = need
-                if need and dview and int(_lib.path_option("HSG_PIECE_MIN", str(PIECE_MIN))) >= PIECE_MIN:
-                    # each side's item count from the kept segment lengths: no read-back
-                    for key, side, cnt, ptr_key in (("dwork", 0, ndst, "indptr"), ("swork", 1, ns, "cindptr")):
-                        items = work_items(cnt, nt, self._long(q, side, slots))
-                        if items > 0:
-                            d[key] = self._sized_work_list(lib, cnt, d[ptr_key], nt, items, st)
-                elif need:
+                if need and not any(v.work_lists(b, q, d, ns, ndst, nt, pieces) for v in active
+                                    if hasattr(v, "work_lists")):
                     attach_work_lists(d, ns, ndst, nt)         # today's path, with its read-back
                 G._rel_cache[("rel", kind, str(dev))] = Relation.on_device(kind, ns, ndst, d, E)
-            if view:
-                t = dict(sent_nodes=new(n_s, i64), sent_ids=new((n_s, L), i64), sent_pos=new(n_s, i64),
-                         sent_len=new(n_s, i64), rowoff=new(n_s + 1, i32), doc_off=new(B + 1, i32),
-                         prev=new((n_s, 2), i64), tfidf_index=new(E, i64))
-                _lib.check(lib.hsg_res_model(cs, p(self._view_cols["tok_len"]), p(self._view_cols["tok_row"]), B,
-                                             p(pick), p(offs), p(rowbase_d), n_s, E, *[p(v) for v in t.values()], st),
-                           "hsg_res_model")
-                glen = [int(x) for x in self.counts[slots, SENT]]
-                G._set_view(ModelInputs(glen, rowbase[B], 1 + int(self.distinct[slots].sum()), self.max_token, **t))
-                # under the keys HiGraph._cached uses; the word nodes are the W2S relation's sources
-                words = G._rel_cache[("rel", "W2S", str(dev))].dev["src_nodes"]
-                for key, val in zip(VIEW_KEYS, (words, t["sent_nodes"], glen, t["tfidf_index"], t["doc_off"])):
-                    G._rel_cache[(key, str(dev))] = val
-            if dview:
-                from .head import HeadLayout
-                sizes = dict(pair_s=n_pr, pair_d=n_pr, super_pos=n_su, sent_super=n_s, doc_super=n_s, super_src=n_su,
-                             doc_ptr=n_dn + 1, doc_sent=n_pr, sent_ptr=n_s + 1, sent_doc=n_pr, sent_row=n_s,
-                             doc_row=n_dn, sup_sent=n_su, sup_ptr=n_su + 1, sup_list=n_s)
-                lay = {k: new(sizes[k], i64) for k in HDSG_DICT}
-                inv_cnt = new(n_dn, f32)
-                lists = {k: new(sizes[k], i32) for k in HDSG_HEAD}
-                _lib.check(lib.hsg_res_hdsg(cs, ctypes.byref(self._hdsg_cstruct), B, p(pick), p(offs), p(docbase_d),
-                                            p(pairbase_d), n_s, n_dn, n_pr, n_su, *[p(v) for v in lay.values()],
-                                            p(inv_cnt), *[p(v) for v in lists.values()], st), "hsg_res_hdsg")
-                # under the keys HiGraph._hdsg_layout / _hdsg_head_layout use
-                G._rel_cache[(HDSG_KEYS[0], str(dev))] = dict(lay, inv_cnt=inv_cnt, n_docs=n_dn)
-                G._rel_cache[(HDSG_KEYS[1], str(dev))] = HeadLayout.prebuilt(n_s, n_dn, n_su, inv_cnt, **lists)
-            if eview:
-                pack = new(n_s + 1 + max(n_w, 1), i32)
-                _lib.check(lib.hsg_res_eval(cs, ctypes.byref(self._eval_cstruct), B, p(pick), p(offs), p(wordbase_d),
-                                            n_s, n_w, p(pack), st), "hsg_res_eval")
-                G.eval_pack = ResidentWordPack(pack, n_s, B, n_w, [int(x) for x in self.counts[slots, SENT]], self,
-                                               slots)
+            for v in active:                            # each view gets its own slices of the copy back
+                v.assemble(b, host[v], arrived[:len(host[v])])
+                del arrived[:len(host[v])]
             # the launches above read pick and offs after this returns: the allocator keeps a
             # freed block for later work of the SAME stream, so dropping them here is safe
         if self.eval_words is not None:
@@ -897,10 +981,7 @@ class ResidentLoader:
         return out
 
     def __iter__(self):
-        kw = {} if self.model_view is None else {"model_view": self.model_view}     # None: the store's default
-        if self.doc_view is not None:
-            kw["doc_view"] = self.doc_view
-        if self.eval_view is not None:
-            kw["eval_view"] = self.eval_view
+        # a flag left at None is not passed (the store's default): whatever has the store's ``batch(idx)`` serves
+        kw = {k: getattr(self, k) for k in ("model_view", "doc_view", "eval_view") if getattr(self, k) is not None}
         for idx in self.batches():
             yield self.store.batch(idx, **kw)

@@ -96,7 +96,7 @@ def main():
     emit({"config": "cfg2", "store_docs": args.store, "docs_per_batch": B, "sentences_per_batch": sum(counts[:B]),
           "words_per_batch": int(stores["words"].words_of[:B].sum()), "paths": paths,
           "eval_view_bytes_per_doc": round(sum(t.numel() * t.element_size()
-                                               for t in stores["words"]._eval_cols.values()) / args.store),
+                                               for t in stores["words"].views["eval_view"].tensors()) / args.store),
           "eval_view_default": DocumentStore.EVAL_VIEW})
     for leg in range(len(LEGS)):
         run(leg, args.warmup)
